@@ -28,6 +28,9 @@ Rank 0 prints ONE JSON line with the contract fields plus
                    Qwen3-14B layer step against ~2k cached tokens, one 256 x 256 ae_d16c32 decode), extrapolated to one image
                    by counts only -- and, from the same sample, "parity": the max / mean error of the HIP path against that
                    oracle output on identical inputs
+
+``--dump-outputs DIR`` writes what the last timed step returned (the decoded images) as DIR/image.npy, float32: weights, prompts
+and noise are seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -100,10 +103,45 @@ def parse():
                          "fp8a: also e4m3 activations (per-row scales) on the fp8 matrix pipe for the GEMMs fed by a row kernel")
     ap.add_argument("--attn-splits", type=int, default=None, help="KV splits of the LLM decode attention (default: 12 beyond 2k cached tokens, else 8)")
     ap.add_argument("--tune", default="", help="comma list name.S=4,name.nw=2,kw2=0 overriding GEMM launch configs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, at most 64 MB in all; "
+                         "a larger output is cut to a fixed, seeded sample of whole items)")
     a = ap.parse_args()
     if a.workload is None:
         a.workload = "tiny" if a.size == "tiny" else "14b-64x-1024"
     return a
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(d: str, arrays: dict) -> None:
+    """--dump-outputs: every ``name -> tensor`` the last timed step returned, as ``d/<name>.npy`` in float32.  An array over its share
+    of DUMP_BYTES keeps a fixed, seeded sample of whole items along dim 0 (the same items for the same shape, in index order); an
+    item that alone exceeds the share keeps a seeded sample of its flattened elements instead.  Inputs are seeded, so two builds
+    run with the same arguments can be compared file for file."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu()
+        if a.numel() * 4 > share:
+            g = torch.Generator().manual_seed(0)
+            if a.dim() > 0 and a[0].numel() * 4 <= share:
+                a = a[torch.randperm(a.shape[0], generator=g)[: share // (a[0].numel() * 4)].sort().values]
+            else:
+                a = a.flatten()[torch.randperm(a.numel(), generator=g)[: share // 4].sort().values]
+        np.save(os.path.join(d, f"{name}.npy"), a.contiguous().numpy())
+
+
+def native_library_current(bd) -> bool:
+    """True iff the built library is newer than every kernel source and header it is made from (modification times only, nothing
+    written).  bench.py builds only when this is False: a current tree that this user may not write is measured as built, also where
+    build() takes its file lock before its own up-to-date check (earlier commits), and a stale one goes through build() and fails
+    there if it cannot be rebuilt."""
+    inputs = [os.path.join(bd.CSRC, f) for f in os.listdir(bd.CSRC)]
+    inputs.append(os.path.join(os.path.dirname(bd.HERE), "include", "bitdance_hip.h"))
+    return bd._newer(bd.LIB, inputs)
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -420,10 +458,11 @@ def main():
     dist, world, rank, dev = setup_dist()
     if args.gpus != world and rank == 0:
         print(f"[bench] note: --gpus {args.gpus} but WORLD_SIZE={world}; using WORLD_SIZE", file=sys.stderr)
+    from bitdance_amd import build as bd
     from bitdance_amd import synthetic as syn
-    from bitdance_amd.build import build
     from bitdance_amd.dist_util import max_over_ranks, rank_seed
-    build(verbose=False)
+    if not native_library_current(bd):
+        bd.build(verbose=False)
     tune = {}
     for kv in filter(None, args.tune.split(",")):
         k, v = kv.split("=")
@@ -585,6 +624,8 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     assert torch.isfinite(img).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"image": img})
     if tp_mode:
         # every rank must hold bit-identical tokens for every timed image.  A divergence (an ordering problem of the hand-written
         # exchange that the warm-up comparison did not catch) makes the timing meaningless as a result -- but a crash would leave the node
@@ -766,6 +807,8 @@ def bench_imagenet(args, dist, world, rank, dev, metric, barrier, max_over_ranks
     barrier()
     dt = max_over_ranks(time.perf_counter() - t0, dist, "cpu" if (dist is not None and dist.get_backend() == "gloo") else dev)
     assert torch.isfinite(out_img.float()).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"image": out_img})
     if rank == 0:
         images = world * n_cls * args.steps
         ar_steps = (256 // 16) ** 2 // P
@@ -828,6 +871,8 @@ def bench_ae_decode(args, dist, world, rank, dev, metric, barrier, max_over_rank
     barrier()
     dt = max_over_ranks(time.perf_counter() - t0, dist, "cpu" if (dist is not None and dist.get_backend() == "gloo") else dev)
     assert torch.isfinite(out.float()).all() and out.shape == (n_img, 3, H, W)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"image": out})
     if rank == 0:
         # algorithmic FLOPs of the decoder's convolutions (2 * pixels * taps * Cin * Cout each), from the module itself
         flops = 0

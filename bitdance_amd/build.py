@@ -38,17 +38,20 @@ def build(force: bool = False, verbose: bool = True, stamp: bool = False) -> str
     ``stamp``: the MEASUREMENT build libbitdance_hip_stamp.so (-DBD_GEMM_STAMP: in-kernel phase stamps, csrc/bd_common.h) that
     tools/launch_anatomy.py loads instead of the product library; the product build compiles none of that code."""
     obj = OBJ + ("_stamp" if stamp else "")
+    lib = LIB.replace(".so", "_stamp.so") if stamp else LIB
+    if not force and _plan(False, obj, lib)[2]:
+        return lib                  # up to date: nothing is written, so a tree this process may not write (built by another user) loads as built
     os.makedirs(obj, exist_ok=True)
     with open(os.path.join(obj, ".lock"), "w") as lock:
         fcntl.flock(lock, fcntl.LOCK_EX)
         try:
-            return _build_locked(force, verbose, obj, LIB.replace(".so", "_stamp.so") if stamp else LIB,
-                                 FLAGS + (["-DBD_GEMM_STAMP"] if stamp else []))
+            return _build_locked(force, verbose, obj, lib, FLAGS + (["-DBD_GEMM_STAMP"] if stamp else []))
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
 
 
-def _build_locked(force: bool, verbose: bool, OBJ: str = OBJ, LIB: str = LIB, FLAGS: list = FLAGS) -> str:
+def _plan(force: bool, OBJ: str, LIB: str) -> tuple:
+    """(compile jobs, object files, True iff the library is up to date): modification times only, nothing is written."""
     headers = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")]
     headers.append(os.path.join(os.path.dirname(HERE), "include", "bitdance_hip.h"))
     jobs = []
@@ -59,7 +62,12 @@ def _build_locked(force: bool, verbose: bool, OBJ: str = OBJ, LIB: str = LIB, FL
         objs.append(o)
         if force or not _newer(o, [s] + headers):
             jobs.append((s, o))
-    if not jobs and _newer(LIB, objs):
+    return jobs, objs, not jobs and _newer(LIB, objs)
+
+
+def _build_locked(force: bool, verbose: bool, OBJ: str = OBJ, LIB: str = LIB, FLAGS: list = FLAGS) -> str:
+    jobs, objs, current = _plan(force, OBJ, LIB)
+    if current:
         return LIB
     hipcc = _hipcc()
 

@@ -3,8 +3,9 @@ import sys
 
 # tests/test_gpu_tp.py runs up to 4 tensor-parallel "ranks" as streams of ONE process whose kernels wait for each other:
 # every such stream needs its own hardware queue (the HIP runtime multiplexes streams onto 4 by default; 32 = one per stream of torch's pool).  Read at HIP
-# initialisation, so it has to be set before the first device call of the test session.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
+# initialisation, so it has to be set before the first device call of the test session -- and set, not defaulted: an environment that
+# already carries the runtime's default of 4 would otherwise put two waiting ranks on one queue and fail every 4-rank test.
+os.environ["GPU_MAX_HW_QUEUES"] = "32"
 
 import pytest
 

@@ -1485,6 +1485,32 @@ def test_bench_contract_on_tiny_workload():
     assert cb["parity"]["within_bounds"] is True
 
 
+def test_bench_dump_outputs_repeat_bit_for_bit(tmp_path):
+    """bench.py --dump-outputs: the images of the last timed step as float32 .npy.  Pass i of a run draws its noise from seed i, so
+    the last timed step is pass warmup + steps - 1: --warmup 3 --steps 1 (another run) must dump exactly what --warmup 1 --steps 3
+    dumped -- the inputs repeat from run to run and --steps sets how many passes are timed -- and --warmup 1 --steps 2 must not."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    imgs = {}
+    for warmup, steps in ((1, 3), (3, 1), (1, 2)):
+        out = tmp_path / f"w{warmup}s{steps}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "tiny", "--steps", str(steps), "--warmup",
+                            str(warmup), "--no-cpu-baseline", "--no-roofline", "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == steps and d["ms_per_step"] > 0
+        imgs[warmup, steps] = np.load(out / "image.npy")
+    a = imgs[1, 3]
+    assert a.dtype == np.float32 and a.shape == (1, 3, 256, 256) and np.isfinite(a).all()
+    assert np.array_equal(a, imgs[3, 1])
+    assert not np.array_equal(a, imgs[1, 2])
+
+
 def test_decode_image_in_chunks_equals_one_batch():
     """decode_image decodes batches larger than ``decode_chunk`` in chunks (round 6: 32 images at 1024 px ran out of memory in the native
     decoder's work buffers): convolutions and per-sample GroupNorm make the images independent, so the chunked result is the

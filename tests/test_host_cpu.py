@@ -30,6 +30,21 @@ def test_library_exports_every_declared_symbol():
     assert so.bd_version() == 1
 
 
+def test_up_to_date_build_writes_nothing(monkeypatch):
+    """build() on a tree that is already built returns the library without creating or opening anything for writing (no lock
+    file): a tree built by one user loads for another who may not write it."""
+    from bitdance_amd import build
+    lib_path = build.build(verbose=False)
+
+    def refuse(*a, **k):
+        raise AssertionError(f"build() wrote in an up-to-date tree: {a}")
+    monkeypatch.setattr(build, "open", refuse, raising=False)
+    monkeypatch.setattr(build.os, "makedirs", refuse)
+    monkeypatch.setattr(build.os, "replace", refuse)
+    monkeypatch.setattr(build.subprocess, "run", refuse)
+    assert build.build(verbose=False) == lib_path
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     from bitdance_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)
@@ -456,3 +471,56 @@ def test_bench_pmc_annotation_reads_the_committed_passes():
     per4 = [{"name": "head.wo", "splitk": 3, "nwaves": 8, "kparts": 1}, {"name": "head.wo", "splitk": 5, "nwaves": 8, "kparts": 1}]   # (round 6: 3 slabs on the 256 x 128-tile kernel)
     assert b.annotate_pmc(per4, 512).endswith("r06_pmc_gemm_traffic_rows512.json") and "mfma_busy" in per4[0] and "mfma_busy" not in per4[1]
     assert b.pmc_entries(256) == {}
+
+
+def test_bench_builds_only_a_stale_library(tmp_path):
+    """bench.py skips build() only when the library is newer than every kernel source and header (then nothing is written, so a tree
+    this user may not write is measured as built); any newer source or the ABI header makes it call build(), which rebuilds or fails."""
+    import importlib.util
+    import types
+    from bitdance_amd import build
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    pkg, csrc, inc = tmp_path / "pkg", tmp_path / "pkg" / "csrc", tmp_path / "include"
+    csrc.mkdir(parents=True)
+    inc.mkdir()
+    files = [csrc / "k.hip", csrc / "k.h", inc / "bitdance_hip.h"]
+    lib = pkg / "lib.so"
+    for f in files + [lib]:
+        f.write_text("")
+    bd = types.SimpleNamespace(CSRC=str(csrc), HERE=str(pkg), LIB=str(lib), _newer=build._newer)
+    for f in files:
+        os.utime(f, (1000, 1000))
+    os.utime(lib, (2000, 2000))
+    assert b.native_library_current(bd)
+    for f in files:
+        os.utime(f, (3000, 3000))
+        assert not b.native_library_current(bd), f
+        os.utime(f, (1000, 1000))
+    lib.unlink()
+    assert not b.native_library_current(bd)
+
+
+def test_bench_dump_outputs_keeps_the_budget_and_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 .npy files; an output within the budget is written whole, a larger one as the same seeded
+    sample of whole items every time, and one item larger than the budget as a seeded sample of its elements."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    monkeypatch.setattr(b, "DUMP_BYTES", 3 * 4096 * 4)
+    small = torch.randn(2, 3, 8, 8, dtype=torch.bfloat16)
+    big = torch.arange(40 * 4096, dtype=torch.float64).reshape(40, 4096)
+    b.dump_outputs(str(tmp_path / "a"), {"small": small, "big": big})
+    b.dump_outputs(str(tmp_path / "b"), {"small": small, "big": big})
+    s, g = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, small.float().numpy())
+    assert g.dtype == np.float32 and g.shape == (1, 4096) and g.nbytes <= 3 * 4096 * 4 // 2
+    rows = g[:, 0] / 4096
+    assert np.array_equal(g, big[torch.from_numpy(rows).long()].float().numpy())       # whole items, in index order
+    assert np.array_equal(g, np.load(tmp_path / "b" / "big.npy"))                      # the same sample every time
+    monkeypatch.setattr(b, "DUMP_BYTES", 1000 * 4)
+    b.dump_outputs(str(tmp_path / "c"), {"big": big})
+    e = np.load(tmp_path / "c" / "big.npy")
+    assert e.shape == (1000,) and np.all(np.diff(e) > 0) and np.all(np.isin(e, big.flatten().float().numpy()))
