@@ -17,7 +17,11 @@ GPU over disjoint images (what the reference's own multi-GPU evaluation does, ev
 ``imagenet-b16x`` (config 2: class-conditional BitDance-B-16x, 256 px, batch 384, 100 sampling steps, linear CFG 6.1,
 imagenet_gen/sample_ddp_parallel.py:199-214); each prints its own metric name -- only the default is the headline.
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run sets up, warms up, times the steps, writes its outputs if ``--dump-outputs`` is given and prints the line: rank 0
+prints ONE JSON line with the contract fields (and, with N > 1 in tensor parallel, the "tp" object of the checks that decide what is
+timed).  ``--full`` adds everything else the benchmark measures or checks, each with runs of its own after the timed steps:
+  "b4", "throughput" : headline workload on one GPU -- one untimed + one timed gen_image at num_images = 4 and 16 (--no-b4, --no-throughput)
+  "replicas"     : N > 1, tensor parallel -- the same N GPUs as independent replicas (--no-replicas)
   "roofline"     : the dominant kernel family (the weight-streaming / MFMA GEMM), measured live with HIP events on the
                    pipeline's stream: achieved = weight bytes physically streamed by every GEMM launch / time vs the 8 TB/s peak at
                    M <= 256 rows ("algorithmic": N*K*2 per Linear and evaluation over the same time -- a grouped launch serves
@@ -28,6 +32,8 @@ Rank 0 prints ONE JSON line with the contract fields plus
                    Qwen3-14B layer step against ~2k cached tokens, one 256 x 256 ae_d16c32 decode), extrapolated to one image
                    by counts only -- and, from the same sample, "parity": the max / mean error of the HIP path against that
                    oracle output on identical inputs
+(The standalone decoder workloads time their roofline with HIP events around the timed steps themselves: their line carries it
+without ``--full``.)
 
 ``--dump-outputs DIR`` writes what the last timed step returned (the decoded images) as DIR/image.npy, float32: weights, prompts
 and noise are seeded, so two builds run with the same arguments can be compared output for output.
@@ -85,12 +91,15 @@ def parse():
     ap.add_argument("--num-images", type=int, default=None, help="images per gen_image call (imagenet: classes per sample call, default 384)")
     ap.add_argument("--sampling-steps", type=int, default=None)
     ap.add_argument("--guidance", type=float, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-b4", action="store_true", help="headline workload on one GPU: skip the extra num_images=4 point (SURVEY 8(d): the eval scripts' batch)")
-    ap.add_argument("--no-throughput", action="store_true", help="headline workload on one GPU: skip the extra saturated-batch point")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline does not need: roofline, the b4 and throughput "
+                         "points, cpu_baseline with its parity, the independent-replicas point (the --no-* switches below drop single items)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip roofline")
+    ap.add_argument("--no-b4", action="store_true", help="--full, headline workload on one GPU: skip the extra num_images=4 point (SURVEY 8(d): the eval scripts' batch)")
+    ap.add_argument("--no-throughput", action="store_true", help="--full, headline workload on one GPU: skip the extra saturated-batch point")
     ap.add_argument("--throughput-images", type=int, default=16, help="num_images of the `throughput` point (default 16: where one GPU saturates -- 0.55 / 0.575 / 0.576 images/s at 8 / 16 / 32)")
-    ap.add_argument("--no-replicas", action="store_true", help="N > 1, tensor parallel: skip the independent-replicas point timed after the tensor-parallel pass")
+    ap.add_argument("--no-replicas", action="store_true", help="--full, N > 1, tensor parallel: skip the independent-replicas point timed after the tensor-parallel pass")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-decode", action="store_true", help="imagenet: skip the conv decoder in the timed pass")
     ap.add_argument("--tp-ada-split", default="auto", choices=["auto", "0", "1"],
@@ -109,6 +118,8 @@ def parse():
     a = ap.parse_args()
     if a.workload is None:
         a.workload = "tiny" if a.size == "tiny" else "14b-64x-1024"
+    if not a.full:                                             # a plain run: the headline line and nothing after the timed steps
+        a.no_cpu_baseline = a.no_roofline = a.no_b4 = a.no_throughput = a.no_replicas = True
     return a
 
 

@@ -524,3 +524,24 @@ def test_bench_dump_outputs_keeps_the_budget_and_a_fixed_sample(tmp_path, monkey
     b.dump_outputs(str(tmp_path / "c"), {"big": big})
     e = np.load(tmp_path / "c" / "big.npy")
     assert e.shape == (1000,) and np.all(np.diff(e) > 0) and np.all(np.isin(e, big.flatten().float().numpy()))
+
+
+def test_bench_plain_run_leaves_the_extras_to_full(monkeypatch):
+    """bench.py without --full does only what its headline needs: every item measured or checked after the timed steps (roofline,
+    b4, throughput, cpu_baseline, replicas) is off.  --full turns them all on, and a --no-* switch still drops its own item there."""
+    import importlib.util
+    import sys
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    extras = ("no_roofline", "no_b4", "no_throughput", "no_cpu_baseline", "no_replicas")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = b.parse()
+    assert not a.full and all(getattr(a, k) for k in extras)
+    assert (a.steps, a.warmup, a.workload, a.dump_outputs) == (3, 1, "14b-64x-1024", None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--warmup", "1", "--full"])
+    a = b.parse()
+    assert a.full and not any(getattr(a, k) for k in extras)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline"])
+    a = b.parse()
+    assert a.no_cpu_baseline and not any(getattr(a, k) for k in extras if k != "no_cpu_baseline")

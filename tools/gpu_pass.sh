@@ -1,6 +1,6 @@
 #!/bin/bash
 # One GPU-box pass (run from the repo root on the box): usage tools/gpu_pass.sh <tag> <steps...>
-#   bench     the default bench line (B = 1 headline + the b4 point + cpu_baseline)
+#   bench     the default bench line with --full (B = 1 headline + roofline + the b4 and throughput points + cpu_baseline)
 #   b4prof    rocprofv3 kernel summary of one num_images=4 image
 #   b1prof    rocprofv3 kernel summary of one num_images=1 image
 #   pmc / pmc512   PMC passes over the GEMM shapes at 128 / 512 rows
@@ -12,7 +12,7 @@ mkdir -p $O
 cd $R
 for step in "$@"; do
   case $step in
-    bench) timeout 400 python bench.py --steps 3 --warmup 1 > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err; tail -c 1500 $O/${TAG}_bench_default.json ;;
+    bench) timeout 400 python bench.py --full --steps 3 --warmup 1 > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err; tail -c 1500 $O/${TAG}_bench_default.json ;;
     b4prof|b1prof|b8prof|b16prof)
       NI=${step#b}; NI=${NI%prof}
       (cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/prof_$step && timeout 300 rocprofv3 --kernel-trace --output-format rocpd -d /tmp/prof_$step -o p -- python $R/bench.py --num-images $NI --steps 1 --warmup 1 --no-roofline --no-cpu-baseline --no-b4 --no-throughput > $O/${TAG}_rocprof_$step.log 2>&1)
