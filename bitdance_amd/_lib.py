@@ -78,6 +78,10 @@ _PROTOS = {
     "bd_graph_capture": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "bd_graph_launch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "bd_step_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "bd_llm_attn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                              C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "bd_in_attn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                             C.c_void_p, C.c_int, C.c_void_p]),
     "bd_prof_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "bd_prof_count": (C.c_int, [C.c_void_p]),
     "bd_prof_get": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.POINTER(C.c_float), C.POINTER(C.c_double)]),

@@ -1400,10 +1400,67 @@ int bd_llm_step(bd_ctx* c, void* s) { BD_GUARD(return llm_step(c, (hipStream_t)s
 int bd_step_reset(bd_ctx* c, const int* kv_len, int nseq, void* s) {
     BD_GUARD(
         if (nseq > BD_MAX_SEQ) return fail("bd_step_reset: nseq > 64");
+        // the step's qkv_post appends P keys at kv_len[i] inside sequence i's Lmax-position cache slice
+        if (c->has_llm)
+            for (int i = 0; i < nseq; ++i)
+                if (kv_len[i] < 0 || kv_len[i] + c->Pn > c->lLmax)
+                    return fail("bd_step_reset: kv_len[" + std::to_string(i) + "] = " + std::to_string(kv_len[i]) + " outside [0, llm.Lmax - P]");
         ResetArgs a; a.state = (BdStepState*)c->wptr("state"); a.nseq = nseq;
         for (int i = 0; i < BD_MAX_SEQ; ++i) a.kv[i] = i < nseq ? kv_len[i] : 0;
         BD_LAUNCH(step_reset_kernel, dim3(1), dim3(64), 0, (hipStream_t)s, a);
         return bd_launch_status() == 0 ? 0 : fail("step_reset launch failed");)
+}
+
+// ---- the decode attentions standalone (tests): host validation, the cache lengths into `state`, then exactly the engine's launch
+static int attn_unsupported(const std::string& m) { g_err = m; return BD_ERR_UNSUPPORTED; }
+static int attn_check_lengths(const int* kv_len, int nseq, int P, int Lmax, const char* who) {
+    for (int i = 0; i < nseq; ++i)
+        if (kv_len[i] < 0 || kv_len[i] + P > Lmax)
+            return attn_unsupported(std::string(who) + ": kv_len[" + std::to_string(i) + "] = " + std::to_string(kv_len[i]) + " outside [0, Lmax - P]");
+    return 0;
+}
+static int attn_write_lengths(void* state, const int* kv_len, int nseq, hipStream_t st) {
+    ResetArgs a; a.state = (BdStepState*)state; a.nseq = nseq;
+    for (int i = 0; i < BD_MAX_SEQ; ++i) a.kv[i] = i < nseq ? kv_len[i] : 0;
+    BD_LAUNCH(step_reset_kernel, dim3(1), dim3(64), 0, st, a);
+    return bd_launch_status();
+}
+
+int bd_llm_attn(const void* q, const void* k_cache, const void* vt_cache, const int* kv_len, int nseq, int P, int nh, int nkv, int Lmax,
+                int splits, int causal, void* state, float* o_part, float* ml_part, void* o_frag, int row_blocks, void* stream) {
+    if (nseq < 1 || nseq > BD_MAX_SEQ) return attn_unsupported("bd_llm_attn: 1 <= nseq <= 64");
+    if (P < 1 || P > 64) return attn_unsupported("bd_llm_attn: 1 <= P <= 64");
+    if (nkv < 1 || nh < nkv || nh % nkv) return attn_unsupported("bd_llm_attn: nh a multiple of nkv");
+    if ((nh / nkv) * ((P + 31) / 32) * 64 > 640) return attn_unsupported("bd_llm_attn: G * ceil(P / 32) * 64 > 640 threads");
+    if (Lmax < 64 || Lmax % 64) return attn_unsupported("bd_llm_attn: Lmax a positive multiple of 64");
+    if (splits < 1) return attn_unsupported("bd_llm_attn: splits >= 1");
+    if ((long long)row_blocks * 32 < (long long)nseq * P) return attn_unsupported("bd_llm_attn: row_blocks * 32 < nseq * P");
+    if (int r = attn_check_lengths(kv_len, nseq, P, Lmax, "bd_llm_attn")) return r;
+    hipStream_t st = (hipStream_t)stream;
+    BD_TRY(attn_write_lengths(state, kv_len, nseq, st));
+    LlmAttnArgs aa;
+    aa.q = q; aa.k_cache = k_cache; aa.vt_cache = vt_cache; aa.o_part = o_part; aa.ml_part = ml_part; aa.o_frag = o_frag;
+    aa.state = (const BdStepState*)state;
+    aa.nseq = nseq; aa.P = P; aa.nh = nh; aa.nkv = nkv; aa.Lmax = Lmax; aa.splits = splits; aa.RB = row_blocks; aa.causal = causal != 0;
+    BD_TRY(bdk_llm_attn(aa, st));
+    return 0;
+}
+
+int bd_in_attn(const void* q, const void* k_cache, const void* v_cache, int kv_len, int nseq, int P, int nh, int Lmax, int causal,
+               void* state, void* o_frag, int row_blocks, void* stream) {
+    if (nseq < 1 || nh < 1) return attn_unsupported("bd_in_attn: nseq, nh >= 1");
+    if (Lmax < 64 || Lmax % 64) return attn_unsupported("bd_in_attn: Lmax a positive multiple of 64");
+    if ((long long)row_blocks * 32 < (long long)nseq * P) return attn_unsupported("bd_in_attn: row_blocks * 32 < nseq * P");
+    if (int r = attn_check_lengths(&kv_len, 1, P, Lmax, "bd_in_attn")) return r;
+    const int form = bdk_in_attn_form(P, Lmax);
+    if (form == -2) return attn_unsupported("bd_in_attn: 1 <= P <= 16");
+    if (form < 0) return attn_unsupported("bd_in_attn: Lmax too long for the score rows of the form P takes (LDS)");
+    hipStream_t st = (hipStream_t)stream;
+    BD_TRY(attn_write_lengths(state, &kv_len, 1, st));
+    InAttnArgs aa{q, (const bf16_t*)k_cache, (const bf16_t*)v_cache, o_frag, (const BdStepState*)state, nseq, P, nh, Lmax, row_blocks};
+    aa.causal = causal != 0;
+    BD_TRY(bdk_in_attn(aa, st));
+    return 0;
 }
 
 int bd_prof_enable(bd_ctx* c, int on) {

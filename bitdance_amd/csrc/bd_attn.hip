@@ -649,34 +649,41 @@ __global__ __launch_bounds__(256) void in_attn_small_kernel(InAttnArgs a, int LS
     }
 }
 
+// Dynamic LDS of each form of bdk_in_attn for a cache of Lmax positions (score rows sized for Lmax + 64 keys)
+static int in_attn_small_ls(int Lmax) { return ((Lmax + 64 + 63) & ~63) + 4; }       // row stride in floats
+static size_t in_attn_small_lds(int P, int Lmax) { return (size_t)4 * (P * in_attn_small_ls(Lmax)) * sizeof(float); }
+static int in_attn_mfma_ls(int Lmax) { return ((Lmax + 64 + 63) & ~63) + 8; }        // row stride in bf16: multiple of 8 (16 B reads), off the bank period
+static size_t in_attn_mfma_lds(int Lmax) { return (size_t)4 * (16 * in_attn_mfma_ls(Lmax) + 64 * 64) * sizeof(bf16_t); }
+static size_t in_attn_lds(int Lmax) { return (size_t)(16 * 64 + 64 * 65 + 16 * (Lmax + 64 + 1)) * sizeof(float); }
+
+// The form bdk_in_attn launches for (P, Lmax): 0 = in_attn_small_kernel<P>, 1 = in_attn_mfma_kernel, 2 = in_attn_kernel;
+// -2 = P outside 1..16, -3 = the score rows fit no form's LDS.  Host only: launches nothing (the matrix-pipe form's LDS opt-in
+// is a function attribute).
+int bdk_in_attn_form(int P, int Lmax) {
+    if (P < 1 || P > 16) return -2;
+    if ((P == 1 || P == 4) && in_attn_small_lds(P, Lmax) <= 64 * 1024) return 0;   // the 1x / 4x checkpoints: a wave per (sequence, head)
+    static unsigned long long optin_m = 0;                         // matrix-pipe form: whole 16-token blocks within the per-wave LDS budget
+    if (P == 16 && bd_lds_optin((const void*)in_attn_mfma_kernel, 160 * 1024, &optin_m) && in_attn_mfma_lds(Lmax) <= 160 * 1024) return 1;
+    return in_attn_lds(Lmax) <= 160 * 1024 ? 2 : -3;
+}
+
 int bdk_in_attn(const InAttnArgs& a, hipStream_t st) {
-    if (a.P > 16) return -2;
-    if (a.P == 1 || a.P == 4) {                                    // the 1x / 4x checkpoints: a wave per (sequence, head)
-        const int LS = ((a.Lmax + 64 + 63) & ~63) + 4;             // row stride in floats
-        const size_t lds_s = (size_t)4 * (a.P * LS) * sizeof(float);
-        if (lds_s <= 64 * 1024) {
-            const dim3 grid((a.nseq * a.nh + 3) / 4);
-            if (a.P == 1) BD_LAUNCH(in_attn_small_kernel<1>, grid, dim3(256), lds_s, st, a, LS);
-            else BD_LAUNCH(in_attn_small_kernel<4>, grid, dim3(256), lds_s, st, a, LS);
-            return bd_launch_status();
-        }
+    const int form = bdk_in_attn_form(a.P, a.Lmax);
+    if (form < 0) return form;
+    if (form == 0) {
+        const dim3 grid((a.nseq * a.nh + 3) / 4);
+        const int LS = in_attn_small_ls(a.Lmax);
+        if (a.P == 1) BD_LAUNCH(in_attn_small_kernel<1>, grid, dim3(256), in_attn_small_lds(1, a.Lmax), st, a, LS);
+        else BD_LAUNCH(in_attn_small_kernel<4>, grid, dim3(256), in_attn_small_lds(4, a.Lmax), st, a, LS);
+        return bd_launch_status();
     }
-    {   // matrix-pipe form: whole 16-token blocks, score rows that fit the per-wave LDS budget
-        const int LS = ((a.Lmax + 64 + 63) & ~63) + 8;             // row stride in bf16: multiple of 8 (16 B reads), off the bank period
-        const size_t lds_m = (size_t)4 * (16 * LS + 64 * 64) * sizeof(bf16_t);
-        static unsigned long long optin_m = 0;
-        const bool ok = bd_lds_optin((const void*)in_attn_mfma_kernel, 160 * 1024, &optin_m);
-        if (a.P == 16 && ok && lds_m <= 160 * 1024) {
-            BD_LAUNCH(in_attn_mfma_kernel, dim3((a.nseq * a.nh + 3) / 4), dim3(256), lds_m, st, a, LS);
-            return bd_launch_status();
-        }
+    if (form == 1) {
+        BD_LAUNCH(in_attn_mfma_kernel, dim3((a.nseq * a.nh + 3) / 4), dim3(256), in_attn_mfma_lds(a.Lmax), st, a, in_attn_mfma_ls(a.Lmax));
+        return bd_launch_status();
     }
-    const int Lcap = a.Lmax + 64;
-    const size_t lds = (size_t)(16 * 64 + 64 * 65 + 16 * (Lcap + 1)) * sizeof(float);
-    if (lds > 160 * 1024) return -3;
     static unsigned long long optin = 0;
     if (!bd_lds_optin((const void*)in_attn_kernel, 160 * 1024, &optin)) return -8;
-    BD_LAUNCH(in_attn_kernel, dim3(a.nseq * a.nh), dim3(256), lds, st, a);
+    BD_LAUNCH(in_attn_kernel, dim3(a.nseq * a.nh), dim3(256), in_attn_lds(a.Lmax), st, a);
     return bd_launch_status();
 }
 

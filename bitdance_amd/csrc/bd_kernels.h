@@ -257,6 +257,7 @@ struct InAttnArgs {         // naive_attention with the reference's rounding poi
                             // 0: every cached key and the whole block (a decode block, and the first call's last, bidirectional block)
 };
 int bdk_in_attn(const InAttnArgs& a, hipStream_t st);
+int bdk_in_attn_form(int P, int Lmax);   // 0 small, 1 matrix-pipe, 2 generic form; < 0 refused (host only)
 
 struct StepAdvanceArgs { BdStepState* state; int nseq, P; };
 int bdk_step_advance(const StepAdvanceArgs& a, hipStream_t st);

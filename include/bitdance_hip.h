@@ -126,7 +126,28 @@ int bd_llm_step(bd_ctx* c, void* stream);
 /* ---- the AR step as hipGraphs: phase 0 = head sample (+sign/tokens), phase 1 = projector + LLM step + advance */
 int bd_graph_capture(bd_ctx* c, int phase, void* stream);
 int bd_graph_launch(bd_ctx* c, int phase, void* stream);
-int bd_step_reset(bd_ctx* c, const int* kv_len, int nseq, void* stream);   /* step = 0, kv_len[] after prefill */
+int bd_step_reset(bd_ctx* c, const int* kv_len, int nseq, void* stream);   /* step = 0, kv_len[] after prefill;
+                                                         with an LLM: -1 unless 0 <= kv_len[i] and kv_len[i] + P <= llm.Lmax */
+
+/* ---- the two decode attentions standalone (tests): exactly the launch bd_llm_step makes, on caller buffers.  kv_len: host values
+ *      (tokens already cached; the P new ones sit at kv_len .. kv_len + P - 1), written into `state` (a device BdStepState: 65 int32,
+ *      step then kv_len[64]) by a kernel on `stream`.  o_frag: bf16, fragment-major over row_blocks * 32 rows x the model width
+ *      (row r, column k at ((k / 16 * row_blocks + r / 32) * 64 + r % 32 + 32 * (k / 8 % 2)) * 8 + k % 8), row = seq * P + query.
+ *      Validated on the host before anything is launched; BD_ERR_UNSUPPORTED if nseq > 64, Lmax % 64, kv_len < 0, kv_len + P > Lmax,
+ *      or a shape the kernels do not cover.
+ *      bd_llm_attn: the Qwen3 flash-decode (scores scaled by 128^-0.5), split over the key range into `splits` parts and merged.
+ *      q [nseq * P][nh][128], K [seq][nkv][Lmax][128], V^T [seq][nkv][128][Lmax], all bf16; scratch o_part
+ *      [nseq][nkv][splits][G * P][128] fp32 and ml_part [nseq][nkv][splits][G * P][2] fp32, G = nh / nkv with
+ *      G * ceil(P / 32) * 64 <= 640 (one workgroup per kv head; Qwen3-14B: G = 5); 1 <= P <= 64, splits >= 1, nseq <= 64.
+ *      causal 0: every query sees kv_len + P keys; 1: query i sees keys <= kv_len + i.
+ *      bd_in_attn: the ImageNet transformer's attention (head_dim 64, MHA, one kv_len for every sequence).  q [nseq * P][nh * 64],
+ *      already scaled by 64^-0.5; K and V [seq][nh][Lmax][64]; 1 <= P <= 16.  The form (and with it the longest Lmax) follows
+ *      from P and the LDS each form needs: P = 1 / 4 a wave per (sequence, head), P = 16 the matrix-pipe form, else / beyond those
+ *      the generic form. */
+int bd_llm_attn(const void* q, const void* k_cache, const void* vt_cache, const int* kv_len, int nseq, int P, int nh, int nkv,
+                int Lmax, int splits, int causal, void* state, float* o_part, float* ml_part, void* o_frag, int row_blocks, void* stream);
+int bd_in_attn(const void* q, const void* k_cache, const void* v_cache, int kv_len, int nseq, int P, int nh, int Lmax, int causal,
+               void* state, void* o_frag, int row_blocks, void* stream);
 
 /* ---- tensor parallelism over xGMI (no counterpart in the reference, whose multi-GPU mode is replicas,
  *      eval/eval_dpg.py:25-29).  One bd_comm per process/GPU.  bd_comm_create allocates (once, not on the hot path) the
