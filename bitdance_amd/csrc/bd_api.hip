@@ -87,6 +87,8 @@ struct bd_ctx {
     bool wfp8 = false;                    // "wdtype" >= 1: every streamed weight is fp8-e4m3 + "<key>_s" scales (bd_gemm8.hip)
     bool fp8a = false;                    // "wdtype" = 2: ALSO fp8 activations, on the fp8 matrix pipe, for the GEMMs a row kernel feeds
                                           //   (head.ada / qkv / w1, llm.qkv / gu: their weights are packed for it, bd_pack_weight8k)
+    bool fp4 = false;                     // "wdtype" = 3: "wdtype" 2 with THOSE GEMMs' weights stored as MXFP4 (e2m1 nibbles + "<key>_e" E8M0 block
+                                          //   exponents, bd_pack_weight4k; bd_gemm4.hip); every other Linear keeps e4m3 + "<key>_s"
     int tp = 1, tpr = 0;
     int hDl = 0, hHl = 0, lnhl = 0, lnkvl = 0, lFl = 0;
     // "tune.ada_group": evaluations whose adaLN projections run as ONE GEMM (head_ada_group); 1 = one GEMM per evaluation
@@ -313,10 +315,11 @@ static bool known_ptr_key(const std::string& k) {
         return false;
     };
     for (const char* n : {"head.cond_w_s", "head.ada_w_s", "head.ada_w_l_s", "proj.w2_s"}) if (k == n) return true;      // fp8 scales
+    for (const char* n : {"head.ada_w_e", "head.ada_w_l_e"}) if (k == n) return true;                                    // MXFP4 block exponents
     return indexed("head.blk", {"ln1_w", "ln1_b", "ln2_w", "ln2_b", "wqkv", "bqkv", "wo", "bo", "w1", "b1", "w2", "b2",
-                                "wqkv_s", "wo_s", "w1_s", "w2_s"}) ||
+                                "wqkv_s", "wo_s", "w1_s", "w2_s", "wqkv_e", "w1_e"}) ||
            indexed("llm.l", {"in_norm", "post_norm", "q_norm", "k_norm", "wqkv", "wo", "wgu", "wdown",
-                             "wqkv_s", "wo_s", "wgu_s", "wdown_s"});
+                             "wqkv_s", "wo_s", "wgu_s", "wdown_s", "wqkv_e", "wgu_e"});
 }
 
 extern "C" {
@@ -397,6 +400,36 @@ int bd_pack_weight8k(void* dst, const void* src_fp8, int rows, int K, int dst_ro
 int bd_pack_weight8k_swiglu(void* dst, const void* gate_fp8, const void* up_fp8, int F, int K, void* stream) {
     if (F % 16) return fail("bd_pack_weight8k_swiglu: F must be a multiple of 16");
     BD_TRY(bdk_pack_w8k(dst, gate_fp8, up_fp8, F / 16, K, 0, F / 16, 1, (hipStream_t)stream));
+    return 0;
+}
+/* MXFP4 weights for the fp4 x fp8 GEMMs (wdtype 3): e2m1 nibbles [rows][K / 2] + E8M0 exponents [rows][K / 32] -> operand order */
+static int unsupported(const std::string& m) { g_err = m; return BD_ERR_UNSUPPORTED; }
+int bd_pack_weight4k(void* dst, void* dst_exp, const void* src_codes, const void* src_exp, int rows, int K, int dst_row0, int dst_rows_total,
+                     void* stream) {
+    if (rows % 32 || dst_row0 % 32 || dst_rows_total % 32 || rows < 0 || dst_row0 < 0 || dst_row0 + rows > dst_rows_total)
+        return fail("bd_pack_weight4k: rows, dst_row0, dst_rows_total must be multiples of 32 and nest");
+    if (K < 64 || K % 64) return unsupported("bd_pack_weight4k: K must be a multiple of 64");
+    if (!dst || !dst_exp || !src_codes || !src_exp) return fail("bd_pack_weight4k: null pointer");
+    BD_TRY(bdk_pack_w4k(dst, dst_exp, src_codes, src_exp, nullptr, nullptr, rows / 32, K, dst_row0 / 32, dst_rows_total / 32, 0, (hipStream_t)stream));
+    return 0;
+}
+int bd_pack_weight4k_swiglu(void* dst, void* dst_exp, const void* gate_codes, const void* gate_exp, const void* up_codes, const void* up_exp,
+                            int F, int K, void* stream) {
+    if (F % 16 || F < 16) return fail("bd_pack_weight4k_swiglu: F must be a multiple of 16");
+    if (K < 64 || K % 64) return unsupported("bd_pack_weight4k_swiglu: K must be a multiple of 64");
+    if (!dst || !dst_exp || !gate_codes || !gate_exp || !up_codes || !up_exp) return fail("bd_pack_weight4k_swiglu: null pointer");
+    BD_TRY(bdk_pack_w4k(dst, dst_exp, gate_codes, gate_exp, up_codes, up_exp, F / 16, K, 0, F / 16, 1, (hipStream_t)stream));
+    return 0;
+}
+/* standalone fp4 x fp8 GEMM (tests): bd_gemm_w8a8 with the packed exponent stream in place of the per-channel scales */
+int bd_gemm_w4a8(const void* a8, const float* ascale, int RB, const void* w4k, const void* wexp, const void* bias, int N, int K, int S, int nw,
+                 int epi, float* scratch, int* counters, void* out, void* stream) {
+    if (!wexp) return unsupported("bd_gemm_w4a8: the exponent stream is required (MXFP4 has no other weight scale)");
+    if (K < 64 || K % 64) return unsupported("bd_gemm_w4a8: K must be a multiple of 64 (one exponent per 32 k, two per MFMA)");
+    if (!a8 || !ascale || !w4k || !out) return fail("bd_gemm_w4a8: null operand");
+    if (epi < 0 || epi > 3) return fail("bd_gemm_w4a8: epi 0 = fp32 slabs, 1 = SwiGLU, 2 = bf16(+bias), 3 = fp32 sum");
+    BD_TRY(bdk_gemm4a(a8, ascale, RB, w4k, wexp, N, K, S, nw, epi, epi == BD_EPI_PARTIAL ? (float*)out : scratch,
+                      epi == BD_EPI_PARTIAL ? nullptr : out, bias, counters, (hipStream_t)stream));
     return 0;
 }
 /* standalone fp8 x fp8 GEMM (tests): a8 / ascale = fp8 activations in the A8 layout + per-row scales (bd_quant_rows8) */
@@ -492,8 +525,14 @@ int bd_ctx_finalize(bd_ctx* c) {
         c->has_head = c->I.count("head.D") > 0;
         c->has_llm = c->I.count("llm.D") > 0;
         c->has_proj = c->I.count("proj.D") > 0;
-        c->wfp8 = c->geti("wdtype", 0) >= 1;
-        c->fp8a = c->geti("wdtype", 0) == 2;
+        const long long wdtype = c->geti("wdtype", 0);
+        if (wdtype < 0 || wdtype > 3) return fail("wdtype: 0 bf16, 1 fp8 weights, 2 fp8 weights + activations, 3 MXFP4 weights + fp8 activations");
+        c->wfp8 = wdtype >= 1;
+        c->fp8a = wdtype == 2 || wdtype == 3;                // (mode 3 differs from mode 2 in the storage of five weight tensors only)
+        c->fp4 = wdtype == 3;
+        if (c->fp4 && ((c->has_llm && c->geti("llm.variant", 0) != 0) || (c->has_head && c->geti("head.variant", 0) != 0) ||
+                       (c->has_proj && c->geti("proj.variant", 0) != 0)))
+            return unsupported("wdtype 3 (MXFP4 weights, fp8 activations): the T2I paths only");
         if (c->fp8a && c->has_llm && c->geti("llm.variant", 0) != 0) return fail("wdtype 2 (fp8 activations): the T2I paths only");
         // the step state has BD_MAX_SEQ (64) per-sequence KV-length slots: a limit of the Qwen3 decode path only (prompts differ in
         // length); head-only contexts read just the step counter, imagenet sequences all share slot 0
@@ -718,10 +757,12 @@ int bd_head_set_cfg(bd_ctx* c, float cfg) {
 // every weight-streaming GEMM of the step goes through here; with profiling on (eager mode only) each launch is
 // bracketed by HIP events on the launch stream so bench.py can report in-situ per-launch durations.
 // a streamed weight: packed bf16, or packed fp8-e4m3 + per-output-channel fp32 scales ("<key>_s") when the context is fp8
-struct WRef { const void* w; const float* s; const float* a = nullptr; };   // a: per-row scales of an fp8 ACTIVATION operand (wdtype 2)
-static WRef wref(const bd_ctx* c, const std::string& key, const char* ascale_ws = nullptr) {
+struct WRef { const void* w; const float* s; const float* a = nullptr;      // a: per-row scales of an fp8 ACTIVATION operand (wdtype 2 / 3)
+              const void* e = nullptr; };                                   // e: MXFP4 weights, the packed exponent stream (wdtype 3; s is null)
+static WRef wref(const bd_ctx* c, const std::string& key, const char* ascale_ws = nullptr, bool act8 = false) {
     WRef r{c->ptr(key), nullptr};
-    if (c->wfp8) r.s = (const float*)c->ptr(key + "_s");
+    if (c->fp4 && (ascale_ws || act8)) r.e = c->ptr(key + "_e");            // the GEMMs on the fp8 matrix pipe: MXFP4 in mode 3
+    else if (c->wfp8) r.s = (const float*)c->ptr(key + "_s");
     if (c->fp8a && ascale_ws) r.a = (const float*)c->ptr(ascale_ws);
     return r;
 }
@@ -730,7 +771,7 @@ static int gemm(bd_ctx* c, const char* name, const void* A, int RB, WRef W, int 
                 float* out, void* act, const void* bias, hipStream_t st) {
     bd_ctx::ProfRec r;
     if (c->prof_on) {
-        r.name = name; r.bytes = (double)N * K * (W.s ? 1 : 2);
+        r.name = name; r.bytes = (double)N * K * (W.e ? 0.53125 : W.s ? 1 : 2);       // (MXFP4: 4 bits + one exponent byte per 32)
         hipEventCreate(&r.e0); hipEventCreate(&r.e1);
         hipEventRecord(r.e0, st);
     }
@@ -738,7 +779,9 @@ static int gemm(bd_ctx* c, const char* name, const void* A, int RB, WRef W, int 
 #ifdef BD_GEMM_STAMP
     bdk_stamp_label(name);
 #endif
-    const int rc = W.a ? bdk_gemm8a(A, W.a, RB, W.w, W.s, N, K, S, nw, epi, out, act, bias, cnt, st)
+    if (W.e && !W.a) return fail(std::string(name) + ": MXFP4 weights need an fp8 activation operand");
+    const int rc = W.e ? bdk_gemm4a(A, W.a, RB, W.w, W.e, N, K, S, nw, epi, out, act, bias, cnt, st)
+                 : W.a ? bdk_gemm8a(A, W.a, RB, W.w, W.s, N, K, S, nw, epi, out, act, bias, cnt, st)
                        : bdk_gemm(A, RB, W.w, N, K, S, nw, epi, out, act, bias, cnt, st, W.s);
     if (c->prof_on) { hipEventRecord(r.e1, st); c->prof.push_back(r); }
     return rc;
@@ -883,7 +926,7 @@ static int head_ada(bd_ctx* c, int i, int buf, hipStream_t st) {
     }
     GemmCfg ga = c->cfg("head.ada");
     bf16_t* out = (bf16_t*)c->wptr("head.ada_bf") + (size_t)buf * c->Mpad * c->hNada;
-    WRef wa = wref(c, "head.ada_w");
+    WRef wa = wref(c, "head.ada_w", nullptr, true);
     wa.a = ysc;
     BD_TRY(gemm(c, "head.ada", y, RB, wa, c->hNada, D, 1, ga.code(), BD_EPI_BF16,
                 nullptr, out, c->ptr("head.ada_b"), st));
@@ -900,7 +943,7 @@ static int head_ada_group(bd_ctx* c, int g, hipStream_t st) {
     char name[32];
     std::snprintf(name, sizeof(name), "head.ada[x%d]", Gg);     // profiling: Gg evaluations' worth of rows per weight pass
     const bool split = c->tp > 1 && c->geti("tp.ada_split", 0) != 0;
-    WRef wa = wref(c, split ? "head.ada_w_l" : "head.ada_w");
+    WRef wa = wref(c, split ? "head.ada_w_l" : "head.ada_w", nullptr, true);
     if (c->fp8a) wa.a = (const float*)c->ptr("head.y_scale_all") + (size_t)g * G * c->Mpad;
     const int nw = (int)c->geti("tune.ada_group_nw", c->fp8a ? 4 : 8) + 16 * 2;   // 8 waves, ring 2: the 256-row / tiled kernels
     if (split) {

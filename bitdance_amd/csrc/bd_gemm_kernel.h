@@ -35,6 +35,16 @@ BD_DEV f32x16 mfma32_f8(u32x4 a0, u32x4 a1, u32x4 b0, u32x4 b1, f32x16 c) {
     return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
 }
 
+// MXFP4 weights x fp8 activations on the same instruction (WT = 3): B format e2m1 (blgp 4: the lane's 32 nibbles of row lane & 31,
+// k = (lane >> 5) * 32 + nibble index, low nibble first, in FOUR registers), A format e4m3 with block scale 2^0 (a0 = k 16 (lane >> 5)
+// + 0..15, a1 = k 32 + 16 (lane >> 5) + 0..15: NOT how mfma32_f8's callers fill them, see gemm_body), and the lane's E8M0 exponent of
+// (row lane & 31, k block lane >> 5) in byte 0 of the B scale operand (tests/test_gpu_fp4.py pins every position)
+BD_DEV f32x16 mfma32_f8f4(u32x4 a0, u32x4 a1, u32x4 b0, unsigned bscale, f32x16 c) {
+    const bd_i32x8 a = {(int)a0[0], (int)a0[1], (int)a0[2], (int)a0[3], (int)a1[0], (int)a1[1], (int)a1[2], (int)a1[3]};
+    const bd_i32x8 b = {(int)b0[0], (int)b0[1], (int)b0[2], (int)b0[3], 0, 0, 0, 0};
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, c, 0, 4, 0, 0x7f7f7f7f, 0, (int)bscale);
+}
+
 struct GemmP {
     const u32x4* A;      // fragment-major activations, RB row-blocks
     const u32x4* W;      // packed weights
@@ -43,6 +53,7 @@ struct GemmP {
     const bf16_t* bias;  // EPI_SWIGLU : [N] in PACKED row order (or null); EPI_BF16: [N] (or null)
     int* cnt;            // EPI_BF16 / EPI_SWIGLU with S > 1: one arrival counter per output tile (zero between launches)
     const float* wscale; // fp8 weights: per packed output row [N] fp32 dequantisation scale (null for bf16 weights)
+                         // WT = 3 (MXFP4): the E8M0 exponent stream instead, dwords [N/32 panels][ceil(K/256)][64 lanes] (bd_gemm4.hip)
     int RB, N, K, S, Mpad;
     size_t PS, SS;       // packed-W strides in 16 B units: panel stride, 64-deep-K-stage stride
     const float* ascale = nullptr;   // fp8 ACTIVATIONS (WT = 2): per row [Mpad] fp32 dequantisation scale
@@ -82,16 +93,27 @@ int bdk_gemm_half(const GemmP& p, int epi, hipStream_t st);
 // of four bf16 ones at twice the rate, and half the LDS bytes for the activations.  Weights: 2 KiB per (panel, 64-deep stage) as
 // two lane-linear 1 KiB halves (bytes 0-15 / 16-31 of every lane's 32); activations: the same chunk shape per (stage, row block),
 // produced by the row kernels together with one fp32 scale per row (bd_rows.hip quant8_store).
+// WT = 3: MXFP4 weights (e2m1 nibbles, one E8M0 exponent per 32 k of a row) x the fp8 activations of WT = 2, same instruction with the
+// B format switched and real block scales.  Weights: 1 KiB per (panel, 64-deep stage), ONE 16 B load per lane (its 32 nibbles).
+// Exponents: a second stream, one dword per lane and FOUR consecutive 64-deep stages (byte b = stage 4 g + b), loaded with every
+// weight stage into a ring slot of its own (the three re-reads of a dword hit the cache; the ring indices stay compile-time) and
+// shifted down to byte 0 by the stage's position: the instruction's byte select is an immediate, the first stage of a K slice is not.
+// No per-channel factor: the block exponents are the whole weight scale.
 // The kernel's body as a device function (the __global__ wrapper follows it): tools/persist_pair.hip runs two bodies inside ONE launch
 // with a grid barrier between them, to price a persistent chain against two launches on this code.
 template <int NP, int KW, int MB, int EPI, int R, bool RED, int MODE = 0, int WT = 0>
 BD_DEV void gemm_body(const GemmP& p) {
-    constexpr int WL = (WT != 0) ? 2 : 4;                 // 16 B loads per lane and 64-deep stage
+    constexpr int WL = (WT == 3) ? 1 : (WT != 0) ? 2 : 4; // 16 B loads per lane and 64-deep stage
+    constexpr bool A8 = (WT >= 2);                        // fp8 activations in the A8 layout
     constexpr bool PIPE = (MODE == 1);
     constexpr int NW = NP * KW, NT = NW * 64;
-    constexpr int UNITS = MB * (WT == 2 ? 128 : 256) * KW; // 16 B units per (64*KW)-deep A stage
+    constexpr int UNITS = MB * (A8 ? 128 : 256) * KW; // 16 B units per (64*KW)-deep A stage
     constexpr int XL = (UNITS + NT - 1) / NT;             // A loads per thread per stage
     constexpr int XR = R - 1;                             // A register-ring slots
+    // WT = 3, an A stage smaller than the workgroup (8 waves at 64 / 32 rows, 4 x 2 at 32): the threads past the stage fetch and store
+    // unit tid % UNITS again (same value to the same LDS word) instead of branching around the load -- with the branch hipcc keeps every
+    // phase's slot live across the unrolled loop and the 64-row form spills (408 B of scratch per lane; straight-line: 0)
+    constexpr bool DUP = (WT == 3) && (UNITS < NT) && (NT % UNITS == 0);
     constexpr int U = (R == 2) ? 8 : 12;
     static_assert(U % R == 0 && U % XR == 0 && U % 2 == 0, "static ring/buffer indices");
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -120,25 +142,33 @@ BD_DEV void gemm_body(const GemmP& p) {
     size_t a_off[XL];
 #pragma unroll
     for (int j = 0; j < XL; ++j) {
-        const int u = tid + j * NT;
+        const int u = DUP ? tid % UNITS : tid + j * NT;
         const int c = u >> 6;
-        if constexpr (WT == 2)
+        if constexpr (A8)
             a_off[j] = ((((size_t)(st0 * KW + c / (2 * MB)) * p.RB) + mt * MB + ((c >> 1) % MB)) * 2 + (c & 1)) * 64 + (u & 63);
         else
             a_off[j] = (((size_t)(st0 * 4 * KW + c / MB) * p.RB) + mt * MB + (c % MB)) * 64 + (u & 63);
     }
-    const size_t a_stage = (WT == 2) ? (size_t)KW * p.RB * 128 : (size_t)4 * KW * p.RB * 64;
+    const size_t a_stage = A8 ? (size_t)KW * p.RB * 128 : (size_t)4 * KW * p.RB * 64;
 
     u32x4 w[R][WL], xr[XR][XL];
+    unsigned we[R] = {};                                    // WT = 3: the exponent dword that covers ring slot r's stage
+    const unsigned* Ep = nullptr;                         // this lane's dword of exponent group 0 of its panel
+    int e_st0 = 0;                                        // 64-deep stage index of this wave's stage 0
+    if constexpr (WT == 3) {
+        Ep = reinterpret_cast<const unsigned*>(p.wscale) + (size_t)nbl * (size_t)(((p.K >> 6) + 3) >> 2) * 64 + lane;
+        e_st0 = st0 * KW + kg;
+    }
     f32x16 acc[MB];
 #pragma unroll
     for (int m = 0; m < MB; ++m)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[m][r] = 0.f;
 
-    auto load_w = [&](u32x4(&wr)[WL], int i) {
+    auto load_w = [&](u32x4(&wr)[WL], int i, [[maybe_unused]] unsigned& er) {
 #pragma unroll
         for (int j = 0; j < WL; ++j) wr[j] = __builtin_nontemporal_load(Wp + (size_t)i * w_stage + j * 64);
+        if constexpr (WT == 3) er = Ep[(size_t)((e_st0 + i * KW) >> 2) * 64];
     };
     auto wop = [&](const u32x4(&wr)[WL], int kk) -> u32x4 {      // B operand of k-step kk of the stage
         if constexpr (WT == 1) return fp8x8_to_bf16x8(wr[kk >> 1][(kk & 1) * 2], wr[kk >> 1][(kk & 1) * 2 + 1]);
@@ -147,18 +177,41 @@ BD_DEV void gemm_body(const GemmP& p) {
     auto load_x = [&](u32x4(&x)[XL], int i) {
 #pragma unroll
         for (int j = 0; j < XL; ++j)
-            if (UNITS % NT == 0 || tid + j * NT < UNITS) x[j] = p.A[a_off[j] + (size_t)i * a_stage];
+            if (UNITS % NT == 0 || DUP || tid + j * NT < UNITS) x[j] = p.A[a_off[j] + (size_t)i * a_stage];
     };
     auto store_x = [&](u32x4* buf, const u32x4(&x)[XL]) {
 #pragma unroll
         for (int j = 0; j < XL; ++j)
-            if (UNITS % NT == 0 || tid + j * NT < UNITS) buf[tid + j * NT] = x[j];
+            if (UNITS % NT == 0 || DUP || tid + j * NT < UNITS) buf[DUP ? tid % UNITS : tid + j * NT] = x[j];
     };
     // This wave's 64-deep part of the A stage goes LDS -> registers in one burst (16 ds_read_b128 for 128 rows), then the
     // MFMAs issue back to back: with the reads interleaved two-at-a-time the matrix pipe idled on LDS latency (the loop
     // was bound by the ds_read -> MFMA chain, not by HBM).
     constexpr int KG = (MB <= 4 && NW <= 8) ? 4 : 1;      // k-steps whose A fragments are resident at once (VGPR budget)
-    auto compute = [&](const u32x4* stage, const u32x4(&wr)[WL]) {
+    auto compute = [&](const u32x4* stage, const u32x4(&wr)[WL], [[maybe_unused]] unsigned er, [[maybe_unused]] int i) {
+        if constexpr (WT == 3) {                                          // one fp8 x fp4 MFMA (K = 64) per row block
+            // The instruction pairs an fp8 lane's registers 0-3 with k = 16 (lane >> 5) + 0..15 and 4-7 with k = 32 + 16 (lane >> 5) + 0..15,
+            // but an fp4 lane's 32 nibbles with k = 32 (lane >> 5) + 0..31 (and its scale byte with exactly those).  fp8 x fp8 never
+            // sees this (both sides permute k alike); here the A fragment is read so that k is the true k: registers 0-3 = the 16 bytes
+            // the A8 layout keeps in half (lane >> 5) of lane (lane & 31), registers 4-7 = the same half of lane 32 + (lane & 31)
+            const u32x4* buf8 = stage + kg * MB * 128 + (lane >> 5) * 64 + (lane & 31);
+            const unsigned sc = er >> (8 * ((e_st0 + i * KW) & 3));       // this stage's exponent byte -> byte 0
+            if constexpr (NW > 8 || MB > 4) {
+#pragma unroll
+                for (int m = 0; m < MB; ++m) {
+                    const u32x4 x0 = buf8[(m * 2) * 64], x1 = buf8[(m * 2) * 64 + 32];
+                    acc[m] = mfma32_f8f4(x0, x1, wr[0], sc, acc[m]);
+                }
+            } else {
+                u32x4 x0[MB], x1[MB];
+#pragma unroll
+                for (int m = 0; m < MB; ++m) { x0[m] = buf8[(m * 2) * 64]; x1[m] = buf8[(m * 2) * 64 + 32]; }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int m = 0; m < MB; ++m) acc[m] = mfma32_f8f4(x0[m], x1[m], wr[0], sc, acc[m]);
+            }
+            return;
+        }
         if constexpr (WT == 2) {                                          // one fp8 MFMA (K = 64) per row block
             const u32x4* buf8 = stage + kg * MB * 128;
             if constexpr (NW > 8 || MB > 4) {                            // 9 / 10 waves (168 registers per wave) or 256 rows (128 accumulator registers): one row block's fragments at a time
@@ -196,7 +249,7 @@ BD_DEV void gemm_body(const GemmP& p) {
     };
 
   if constexpr (PIPE) {
-    static_assert(R == 2 && KG == 4 && WT != 2, "pipelined loop: two W stages in flight, whole-stage fragment sets (bf16 MFMA forms)");
+    static_assert(R == 2 && KG == 4 && WT < 2, "pipelined loop: two W stages in flight, whole-stage fragment sets (bf16 MFMA forms)");
     u32x4 xf[2][4][MB];
     auto read_stage = [&](u32x4(&x)[4][MB], const u32x4* stage) {
         const u32x4* buf = stage + kg * MB * 256;
@@ -215,9 +268,9 @@ BD_DEV void gemm_body(const GemmP& p) {
     };
     // prologue: A stages 0 and 1 in LDS, stage 2 in registers; W stages 0 and 1 in registers; fragments of stage 0 read
     load_x(xr[0], 0);
-    load_w(w[0], 0);
+    load_w(w[0], 0, we[0]);
     store_x(lds, xr[0]);
-    if (1 < nst) { load_x(xr[0], 1); load_w(w[1], 1); store_x(lds + UNITS, xr[0]); }
+    if (1 < nst) { load_x(xr[0], 1); load_w(w[1], 1, we[1]); store_x(lds + UNITS, xr[0]); }
     if (2 < nst) load_x(xr[0], 2);
     __syncthreads();
     read_stage(xf[0], lds);
@@ -230,7 +283,7 @@ BD_DEV void gemm_body(const GemmP& p) {
             mma_stage(xf[ph & 1], w[ph & 1]);                                 // stage j
             store_x(lds + (ph & 1) * UNITS, xr[0]);                           // stage j+2 over stage j's tile
             load_x(xr[0], i + ph + 3);
-            load_w(w[ph & 1], i + ph + 2);
+            load_w(w[ph & 1], i + ph + 2, we[ph & 1]);
             __syncthreads();
         }
     }
@@ -244,7 +297,7 @@ BD_DEV void gemm_body(const GemmP& p) {
             if (j + 2 < nst) {
                 store_x(lds + (ph & 1) * UNITS, xr[0]);
                 if (j + 3 < nst) load_x(xr[0], j + 3);
-                load_w(w[ph & 1], j + 2);
+                load_w(w[ph & 1], j + 2, we[ph & 1]);
             }
             if (j + 1 < nst) __syncthreads();
             else BD_MFMA_DRAIN();                          // the last executed phase branches straight to the accumulator reads (bd_common.h)
@@ -253,10 +306,10 @@ BD_DEV void gemm_body(const GemmP& p) {
   } else {
     // prologue: stages 0..R-1 of A and W in flight; stage q of A lives in ring slot q % XR
     if (p.hw.flags) {                                          // block-uniform: the operand comes from the peers (bd_sp.hip)
-        load_w(w[0], 0);
+        load_w(w[0], 0, we[0]);
 #pragma unroll
         for (int r = 1; r < R; ++r)
-            if (r < nst) load_w(w[r], r);                      // the weight stream starts before the wait ...
+            if (r < nst) load_w(w[r], r, we[r]);                      // the weight stream starts before the wait ...
         gemm_hwait(p.hw, tid, NT);                             // ... which ends when every operand row has landed
         BD_KSTAMP(p.stamp, 1);
         load_x(xr[0], 0);
@@ -266,7 +319,7 @@ BD_DEV void gemm_body(const GemmP& p) {
             if (r < nst) load_x(xr[r % XR], r);
     } else {
         load_x(xr[0], 0);
-        load_w(w[0], 0);
+        load_w(w[0], 0, we[0]);
         store_x(lds, xr[0]);
 #ifdef BD_GEMM_STAMP
         asm volatile("s_waitcnt vmcnt(%0)" :: "n"(WL) : "memory");            // the A stage has landed (W stage 0 still in flight)
@@ -274,7 +327,7 @@ BD_DEV void gemm_body(const GemmP& p) {
 #endif
 #pragma unroll
         for (int r = 1; r < R; ++r)
-            if (r < nst) { load_x(xr[r % XR], r); load_w(w[r], r); }
+            if (r < nst) { load_x(xr[r % XR], r); load_w(w[r], r, we[r]); }
     }
     __syncthreads();
 #ifdef BD_GEMM_STAMP
@@ -288,10 +341,10 @@ BD_DEV void gemm_body(const GemmP& p) {
     for (; i + U + R - 1 < nst; i += U) {
 #pragma unroll
         for (int ph = 0; ph < U; ++ph) {
-            compute(lds + (ph & 1) * UNITS, w[ph % R]);
+            compute(lds + (ph & 1) * UNITS, w[ph % R], we[ph % R], i + ph);
             store_x(lds + ((ph + 1) & 1) * UNITS, xr[(ph + 1) % XR]);
             load_x(xr[(ph + 1) % XR], i + ph + R);          // same slot: (ph + R) % XR == (ph + 1) % XR
-            load_w(w[ph % R], i + ph + R);
+            load_w(w[ph % R], i + ph + R, we[ph % R]);
             __syncthreads();
         }
     }
@@ -300,10 +353,10 @@ BD_DEV void gemm_body(const GemmP& p) {
     for (int ph = 0; ph < U + R - 1; ++ph) {
         const int j = i + ph;
         if (j < nst) {
-            compute(lds + (ph & 1) * UNITS, w[ph % R]);
+            compute(lds + (ph & 1) * UNITS, w[ph % R], we[ph % R], j);
             if (j + 1 < nst) {
                 store_x(lds + ((ph + 1) & 1) * UNITS, xr[(ph + 1) % XR]);
-                if (j + R < nst) { load_x(xr[(ph + 1) % XR], j + R); load_w(w[ph % R], j + R); }
+                if (j + R < nst) { load_x(xr[(ph + 1) % XR], j + R); load_w(w[ph % R], j + R, we[ph % R]); }
                 __syncthreads();
             } else {
                 BD_MFMA_DRAIN();                           // the last executed phase branches straight to the accumulator reads (bd_common.h)
@@ -341,14 +394,14 @@ BD_DEV void gemm_body(const GemmP& p) {
     }
     BD_KSTAMP(p.stamp, 4);
     const bool owner = (kg == 0) && pvalid;                                // the wave that holds the tile's sums
-    if constexpr (WT != 0) {                                               // dequantisation scale of this lane's output column
+    if constexpr (WT == 1 || WT == 2) {                                    // dequantisation scale of this lane's output column
         const float sc = p.wscale[nbl * 32 + (lane & 31)];
 #pragma unroll
         for (int m = 0; m < MB; ++m)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[m][r] *= sc;
     }
-    if constexpr (WT == 2) {                                               // ... and of the activation rows (reg r -> row (r&3)+8(r>>2)+4(lane>>5))
+    if constexpr (A8) {                                                    // ... and of the activation rows (reg r -> row (r&3)+8(r>>2)+4(lane>>5))
 #pragma unroll
         for (int m = 0; m < MB; ++m) {
             const float* as = p.ascale + (mt * MB + m) * 32 + 4 * (lane >> 5);

@@ -39,6 +39,11 @@ int bdk_gemm8(const void* A, int RB, const void* W8, const float* wscale, int N,
 // fp8 weights + fp8 activations on the fp8 matrix pipe (bd_gemm_kernel.h WT = 2)
 int bdk_gemm8a(const void* A8, const float* ascale, int RB, const void* W8k, const float* wscale, int N, int K, int S, int nw, int epi,
                float* out_partial, void* out_act, const void* bias, int* tile_counters, hipStream_t st);
+// MXFP4 weights + fp8 activations on the same pipe (bd_gemm_kernel.h WT = 3, bd_gemm4.hip); wexp: the packed E8M0 exponent stream
+int bdk_gemm4a(const void* A8, const float* ascale, int RB, const void* W4k, const void* wexp, int N, int K, int S, int nw, int epi,
+               float* out_partial, void* out_act, const void* bias, int* tile_counters, hipStream_t st);
+int bdk_pack_w4k(void* dst, void* dst_e, const void* src, const void* src_e, const void* src2, const void* src2_e, int panels, int K, int nb0,
+                 int panels_total, int mode, hipStream_t st);
 int bdk_pack_w8k(void* dst, const void* src_fp8, const void* src2_fp8, int panels, int K, int nb0, int panels_total, int mode, hipStream_t st);
 int bdk_pack_w8(void* dst, const void* src_fp8, const void* src2_fp8, int panels, int K, int nb0, int panels_total, int mode, hipStream_t st);
 int bdk_pack_w(void* dst, const void* src, const void* src2, int panels, int K, int nb0, int panels_total, int mode, hipStream_t st);

@@ -11,7 +11,7 @@ from dataclasses import dataclass, field
 
 import torch
 
-from ._lib import BitDanceHipError, check, lib
+from ._lib import BitDanceHipError, BitDanceUnsupported, check, lib
 
 BF16 = torch.bfloat16
 
@@ -97,16 +97,100 @@ def pack_swiglu_fp8(gate: torch.Tensor, up: torch.Tensor, device, k64: bool = Fa
     return out, scales
 
 
+E2M1_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)   # magnitudes of the OCP e2m1 codes 0..7 (bit 3 of a code = sign)
+MXFP4_BLOCK = 32                                     # consecutive k of one output channel that share an E8M0 exponent
+
+
+def quantize_rows_mxfp4(w: torch.Tensor):
+    """OCP MXFP4 along K, round to nearest even, deterministic: blocks of 32 consecutive k of one output channel share the exponent
+    e = floor(log2(amax)) - 2 (so amax / 2^e lies in [4, 8): the top of the e2m1 range, values above 6 saturate), clamped to the E8M0
+    range [-127, 127]; an all-zero block gets -127.  Element = RNE(w / 2^e) on the e2m1 grid, saturated at +-6.  No per-channel scale.
+    Returns (codes uint8 [N, K] in 0..15, bit 3 = sign; biased exponents uint8 [N, K / 32], value 2^(byte - 127)).  The bf16 weight
+    values are scaled in fp64, where every step before the rounding is exact."""
+    wf = w.detach().to(torch.bfloat16).float()
+    N, K = wf.shape
+    if K % MXFP4_BLOCK:
+        raise BitDanceHipError(f"quantize_rows_mxfp4: K = {K} is not a multiple of {MXFP4_BLOCK}")
+    blk = wf.view(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = blk.abs().amax(dim=2)
+    # floor(log2(amax)) from the fp32 exponent field (amax is a bf16 value: normal in fp32 unless below 2^-126, where the clamp takes over)
+    e = ((amax.view(torch.int32) >> 23) & 0xFF) - 127 - 2
+    e = torch.where(amax == 0, torch.full_like(e, -127), e).clamp(-127, 127)
+    a = blk.double().abs() * torch.exp2(-e.double())[:, :, None]
+    q = torch.where(a < 2, torch.round(a * 2) / 2, torch.where(a < 4, torch.round(a), torch.round(a / 2) * 2)).clamp_max(6.0)
+    code = torch.where(q < 2, q * 2, torch.where(q < 4, q + 2, q / 2 + 4)).to(torch.uint8)
+    code = code | (torch.signbit(blk).to(torch.uint8) << 3)
+    return code.view(N, K).contiguous(), (e + 127).to(torch.uint8).contiguous()
+
+
+def dequantize_mxfp4(codes: torch.Tensor, exps: torch.Tensor) -> torch.Tensor:
+    """The fp64 values of quantize_rows_mxfp4's output: [N, K]."""
+    grid = torch.tensor(E2M1_GRID, dtype=torch.float64, device=codes.device)
+    v = grid[(codes & 7).long()] * (1.0 - 2.0 * (codes >> 3).double())
+    N, K = codes.shape
+    return (v.view(N, K // MXFP4_BLOCK, MXFP4_BLOCK) * torch.exp2(exps.double() - 127.0)[:, :, None]).view(N, K)
+
+
+def mxfp4_nibbles(codes: torch.Tensor) -> torch.Tensor:
+    """codes [N, K] (one per byte) -> [N, K / 2]: k = 2 b in the low nibble of byte b, k = 2 b + 1 in the high one (bd_pack_weight4k)."""
+    return (codes[:, 0::2] | (codes[:, 1::2] << 4)).contiguous()
+
+
+def mxfp4_exp_bytes(n: int, K: int) -> int:
+    """bytes of the packed exponent stream of n rows: one dword per lane and four 64-deep K stages."""
+    return n // 32 * ((K // 64 + 3) // 4) * 256
+
+
+def pack_linear_fp4(ws: list[torch.Tensor], device):
+    """pack_linear for the MXFP4 weight path (``weights="fp4a"``, csrc/bd_gemm4.hip): (packed e2m1 nibbles [n * K / 2] bytes,
+    packed E8M0 exponent stream).  Row-stacked tensors (q / k / v, the adaLN blocks) quantise independently: blocks run along K."""
+    K = ws[0].shape[1]
+    n = sum(w.shape[0] for w in ws)
+    if K % 64 or any(w.shape[0] % 32 or w.shape[1] != K for w in ws):
+        raise BitDanceHipError(f"pack_linear_fp4: unsupported shape N={[w.shape[0] for w in ws]} K={K}")
+    out = torch.empty(n * K // 2, dtype=torch.uint8, device=device)
+    exps = torch.empty(mxfp4_exp_bytes(n, K), dtype=torch.uint8, device=device)
+    row = 0
+    for w in ws:
+        c, e = quantize_rows_mxfp4(w.to(device))
+        nib = mxfp4_nibbles(c)
+        check(lib().bd_pack_weight4k(out.data_ptr(), exps.data_ptr(), nib.data_ptr(), e.data_ptr(), c.shape[0], K, row, n, _stream()),
+              "bd_pack_weight4k")
+        torch.cuda.current_stream().synchronize()
+        row += c.shape[0]
+    return out, exps
+
+
+def pack_swiglu_fp4(gate: torch.Tensor, up: torch.Tensor, device):
+    F_, K = gate.shape
+    if K % 64 or F_ % 32 or up.shape != gate.shape:
+        raise BitDanceHipError(f"pack_swiglu_fp4: unsupported shape F={F_} K={K}")
+    cg, eg = quantize_rows_mxfp4(gate.to(device))
+    cu, eu = quantize_rows_mxfp4(up.to(device))
+    ng, nu = mxfp4_nibbles(cg), mxfp4_nibbles(cu)
+    out = torch.empty(F_ * K, dtype=torch.uint8, device=device)
+    exps = torch.empty(mxfp4_exp_bytes(2 * F_, K), dtype=torch.uint8, device=device)
+    check(lib().bd_pack_weight4k_swiglu(out.data_ptr(), exps.data_ptr(), ng.data_ptr(), eg.data_ptr(), nu.data_ptr(), eu.data_ptr(), F_, K,
+                                        _stream()), "bd_pack_weight4k_swiglu")
+    torch.cuda.current_stream().synchronize()
+    return out, exps
+
+
 def _put_linear(p: dict, key: str, ws: list, device, fp8: int, act8: bool = False) -> None:
-    """``fp8``: 0 bf16, 1 fp8 weights, 2 fp8 weights + (for the GEMMs marked ``act8``: the ones a row kernel feeds) fp8 activations."""
-    if fp8:
+    """``fp8``: 0 bf16, 1 fp8 weights, 2 fp8 weights + (for the GEMMs marked ``act8``: the ones a row kernel feeds) fp8 activations,
+    3 as 2 with the ``act8`` GEMMs' weights stored as MXFP4 (``<key>_e`` = their exponent stream; no ``<key>_s``)."""
+    if fp8 == 3 and act8:
+        p[key], p[key + "_e"] = pack_linear_fp4(ws, device)
+    elif fp8:
         p[key], p[key + "_s"] = pack_linear_fp8(ws, device, k64=(fp8 == 2 and act8))
     else:
         p[key] = pack_linear(ws, device)
 
 
 def _put_swiglu(p: dict, key: str, gate, up, device, fp8: int, act8: bool = False) -> None:
-    if fp8:
+    if fp8 == 3 and act8:
+        p[key], p[key + "_e"] = pack_swiglu_fp4(gate, up, device)
+    elif fp8:
         p[key], p[key + "_s"] = pack_swiglu_fp8(gate, up, device, k64=(fp8 == 2 and act8))
     else:
         p[key] = pack_swiglu(gate, up, device)
@@ -118,8 +202,9 @@ def pack_swiglu_bias(bg: torch.Tensor, bu: torch.Tensor, device) -> torch.Tensor
 
 def _fp8_flag(weights: str) -> int:
     """0 bf16; 1 "fp8": e4m3 weights, bf16 activations; 2 "fp8a": e4m3 weights everywhere + e4m3 activations (per-row scales) on the
-    fp8 matrix pipe for the GEMMs fed by a row kernel (head adaLN / qkv / w1, LLM q/k/v and gate/up)."""
-    modes = {"bf16": 0, "fp8": 1, "fp8a": 2}
+    fp8 matrix pipe for the GEMMs fed by a row kernel (head adaLN / qkv / w1, LLM q/k/v and gate/up); 3 "fp4a": "fp8a" with the weights of
+    those GEMMs stored as MXFP4 (e2m1 + one E8M0 exponent per 32 k, quantize_rows_mxfp4) on the same instruction."""
+    modes = {"bf16": 0, "fp8": 1, "fp8a": 2, "fp4a": 3}
     if weights not in modes:
         raise BitDanceHipError(f"weights must be one of {sorted(modes)}, not {weights!r}")
     return modes[weights]
@@ -177,6 +262,8 @@ class HeadWeights:
                          mlp=mlp)
         hw.tp_size = tp_size
         hw.wdtype = int(fp8)
+        if fp8 == 3 and mlp:
+            raise BitDanceUnsupported('weights="fp4a": the T2I head only (the MLP head of the ImageNet models has no MXFP4 form)')
         p = hw.ptrs
         _put_linear(p, "head.cond_w", [g("net.cond_embed.weight")], device, fp8)
         p["head.cond_b"] = _bf16(g("net.cond_embed.bias"), device)
@@ -201,6 +288,8 @@ class HeadWeights:
             for n, src in ((("2", "norm"),) if mlp else (("1", "norm1"), ("2", "norm2"))):
                 p[d + f"ln{n}_w"] = g(s + src + ".weight").detach().to(device, torch.float32).contiguous()
                 p[d + f"ln{n}_b"] = g(s + src + ".bias").detach().to(device, torch.float32).contiguous()
+            if fp8 == 3:                                     # tensor parallel: the MXFP4 GEMMs are column-split, K (and every block of 32 along it) stays whole
+                assert g(s + "attn.wqkv.weight").shape[1] == D and g(s + "w1.weight").shape[1] == D and all(w_.shape[1] == D for w_ in ada_w)
             if not mlp:
                 _put_linear(p, d + "wqkv", [g(s + "attn.wqkv.weight")], device, fp8, act8=True)
                 p[d + "bqkv"] = _bf16(g(s + "attn.wqkv.bias"), device)
@@ -290,6 +379,8 @@ class LlmWeights:
         for i in range(cfg["num_hidden_layers"]):
             s, d = f"model.layers.{i}.", f"llm.l{i}."
             q, k, v = (sd[s + f"self_attn.{n}_proj.weight"] for n in "qkv")
+            if fp8 == 3:                                     # tensor parallel: the MXFP4 GEMMs are column-split, K (and every block of 32 along it) stays whole
+                assert all(w_.shape[1] == cfg["hidden_size"] for w_ in (q, k, v, sd[s + "mlp.gate_proj.weight"], sd[s + "mlp.up_proj.weight"]))
             _put_linear(p, d + "wqkv", [q, k, v], device, fp8, act8=True)
             _put_linear(p, d + "wo", [sd[s + "self_attn.o_proj.weight"]], device, fp8)
             _put_swiglu(p, d + "wgu", sd[s + "mlp.gate_proj.weight"], sd[s + "mlp.up_proj.weight"], device, fp8, act8=True)
@@ -401,7 +492,7 @@ class Engine:
             mp = 32 if self.M <= 32 else (64 if self.M <= 64 else (self.M + 127) // 128 * 128)
             G = ints.get("tune.ada_group", 512 // mp if mp <= 128 else (1024 // mp if (mp <= 512 and 1024 % mp == 0) else 1))
             need = 2 * G * mp * head.ptrs["head.ada_b"].numel() * 2          # two slots (double-buffered by group parity)
-            self.ada_split = G >= 2 and self.comm.gather_bytes >= need and (self.wdtype in (0, 2))
+            self.ada_split = G >= 2 and self.comm.gather_bytes >= need and (self.wdtype in (0, 2, 3))
         ints["tp.ada_split"] = int(self.ada_split)
         # sequence-parallel row kernels (csrc/bd_sp.hip): every rank owns rows / tp rows of the head's residual stream and no stand-alone
         # exchange kernel is left in an evaluation.  Default wherever the form applies: the hand-written exchange with an operand landing
@@ -536,7 +627,7 @@ class Engine:
         if y_bytes <= (512 << 20):
             self.y_all = torch.zeros(y_bytes // 2, dtype=BF16, device=self.device)
             self.set_ptr("head.y_all", self.y_all)
-            if self.wdtype == 2:                             # fp8 activations: per-row scales of every evaluation's y
+            if self.wdtype in (2, 3):                             # fp8 activations: per-row scales of every evaluation's y
                 self.y_scale_all = torch.zeros(cap * self.Mpad, dtype=torch.float32, device=self.device)
                 self.set_ptr("head.y_scale_all", self.y_scale_all)
             self.set_int("head.y_evals", cap)

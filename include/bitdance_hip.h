@@ -89,6 +89,23 @@ int bd_pack_weight8k_swiglu(void* dst, const void* gate_fp8, const void* up_fp8,
 int bd_quant_rows8(void* a8, float* ascale, const float* src_rows_f32, int M, int K, int RB, void* stream);
 int bd_gemm_w8a8(const void* a8, const float* ascale, int RB, const void* w8k, const float* wscale, const void* bias, int N, int K, int S, int nw,
                  int epi, float* scratch, int* counters, void* out, void* stream);
+/* MXFP4 weights x fp8 activations ("wdtype" 3, weights="fp4a"): "wdtype" 2 with the weights of those same GEMMs stored as OCP MXFP4
+ * along K -- e2m1 elements (0, 0.5, 1, 1.5, 2, 3, 4, 6, signed), one E8M0 exponent byte per 32 consecutive k of an output channel, no
+ * per-channel scale -- on the same instruction with the B format switched to e2m1 and the exponents as its block scales.  Source form:
+ * codes [rows][K / 2] bytes (k = 2 b in the low nibble of byte b, k = 2 b + 1 in the high one; bit 3 of a nibble = sign), exponents
+ * [rows][K / 32] bytes (value 2^(byte - 127)).  Packed: dst = rows_total * K / 2 bytes, dst_exp = rows_total / 32 * ceil(K / 256) * 256
+ * bytes (one dword per lane and four 64-deep K stages).  bd_pack_weight4k writes rows dst_row0 .. + rows of a tensor of dst_rows_total
+ * rows (all multiples of 32); the _swiglu form interleaves 16 gate rows with the 16 matching up rows per panel, as bd_pack_weight8k_swiglu.
+ * bd_gemm_w4a8: bd_gemm_w8a8 with the packed exponent stream in place of wscale (tests); out = accumulator x activation row scale.
+ * K % 64 != 0 or a null exponent stream: BD_ERR_UNSUPPORTED before any launch.  Context form: int "wdtype" = 3, a "<weight key>_e" packed
+ * exponent pointer next to head.ada_w(_l) / blk<i>.wqkv / blk<i>.w1 / llm.l<i>.wqkv / llm.l<i>.wgu and "<weight key>_s" next to every
+ * other streamed weight (e4m3, as in "wdtype" 1 / 2); refused for the ImageNet variants. */
+int bd_pack_weight4k(void* dst, void* dst_exp, const void* src_codes, const void* src_exp, int rows, int K, int dst_row0, int dst_rows_total,
+                     void* stream);
+int bd_pack_weight4k_swiglu(void* dst, void* dst_exp, const void* gate_codes, const void* gate_exp, const void* up_codes, const void* up_exp,
+                            int F, int K, void* stream);
+int bd_gemm_w4a8(const void* a8, const float* ascale, int RB, const void* w4k, const void* wexp, const void* bias, int N, int K, int S, int nw,
+                 int epi, float* scratch, int* counters, void* out, void* stream);
 
 /* ---- context: named ints / floats / device pointers, then finalize.  Keys are listed in INTEGRATION.md (appendix) / bd_api.hip kIntKeys, kPtrKeys; an unknown key is an
  *      error (-1, text in bd_last_error()), never a silent default. */

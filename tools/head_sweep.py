@@ -6,7 +6,7 @@
 (the run-ahead weight prefetch this tool also swept in round 3 -- profiles/r03_head_sweep1.log -- measured negative and is gone)
 
 Every configuration is timed as a hipGraph replay and its sampled latent is compared bit for bit with the first one's.
-python tools/head_sweep.py [reps] [n_steps] ["k=v,k=v;k=v,..." extra configs] [bf16|fp8|fp8a]
+python tools/head_sweep.py [reps] [n_steps] ["k=v,k=v;k=v,..." extra configs] [bf16|fp8|fp8a|fp4a]
 
   --tp-shard r/N [--loopback]   ONE rank's critical path at the tensor-parallel shard shapes on ONE GPU: rank r of N packs its weight
       slices, the communicator runs in loop-back (bd_comm_set_loopback: the peers' buffers are scratch copies, every flag a peer would

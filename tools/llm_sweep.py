@@ -2,8 +2,8 @@
 on ONE box: a 12-layer slice of the model at true dimensions (7.9 GB of packed weights: every layer's weights come from HBM),
 caches ~1k tokens long, the step run eagerly and timed with events on the launch stream, plus the in-situ time of each GEMM.
 
-python tools/llm_sweep.py [reps] ["k=v,k=v;k=v,..." configs] [cached tokens]      keys: llm.<gemm>.{S,nw,kw,ring}, slab3, kparts8, ...,
-                                                                                    splits (flash-decode splits of the attention)"""
+python tools/llm_sweep.py [reps] ["k=v,k=v;k=v,..." configs] [cached tokens] [bf16|fp8|fp8a|fp4a]
+                                                            keys: llm.<gemm>.{S,nw,kw,ring}, slab3, kparts8, ..., splits (flash-decode splits of the attention)"""
 import os
 import sys
 
@@ -44,17 +44,18 @@ def run():
     if len(sys.argv) > 2:
         cfgs = [dict((kv.split("=")[0], int(kv.split("=")[1])) for kv in c.split(",") if kv) for c in sys.argv[2].split(";")]
     dev = "cuda"
+    wmode = sys.argv[4] if len(sys.argv) > 4 else "bf16"
     cfg = dict(syn.QWEN3_14B)
     cfg["num_hidden_layers"] = LAYERS
     cfg["vocab_size"] = 1024
     if shard:
-        lw = E.LlmWeights.from_state_dict(syn.random_llm_state(cfg, dev), cfg, dev, keep_for_prefill=False, tp_rank=shard[0], tp_size=shard[1])
+        lw = E.LlmWeights.from_state_dict(syn.random_llm_state(cfg, dev), cfg, dev, keep_for_prefill=False, tp_rank=shard[0], tp_size=shard[1], weights=wmode)
         print(f"# rank {shard[0]} of {shard[1]} in loop-back: this rank's weight slices, peers' buffers are scratch, flags written locally "
               f"(values are meaningless: the peers contribute zeros)", flush=True)
         if len(sys.argv) <= 2:
             cfgs = [{"tp.llm_seq": 0}, {"tp.llm_seq": 1}, {"tp.llm_seq": 0}, {"tp.llm_seq": 1}]
     else:
-        lw = E.LlmWeights.from_state_dict(syn.random_llm_state(cfg, dev), cfg, dev, keep_for_prefill=False)
+        lw = E.LlmWeights.from_state_dict(syn.random_llm_state(cfg, dev), cfg, dev, keep_for_prefill=False, weights=wmode)
     g = torch.Generator(device=dev).manual_seed(3)
     x = torch.randn(128, cfg["hidden_size"], device=dev, generator=g)
     ref = None
