@@ -366,17 +366,22 @@ int bd_probe_read(const void* src, long long bytes, int blocks, void* sink, void
     return 0;
 }
 int bd_gemm_partial(const void* a, int RB, const void* w, int N, int K, int S, int nw, float* out, void* stream) {
-    BD_TRY(bdk_gemm(a, RB, w, N, K, S, nw, BD_EPI_PARTIAL, out, nullptr, nullptr, nullptr, (hipStream_t)stream));
+    GemmCall g; g.A = a; g.RB = RB; g.W = w; g.N = N; g.K = K; g.S = S; g.nw = nw; g.epi = BD_EPI_PARTIAL; g.out_partial = out;
+    BD_TRY(bdk_gemm_launch(g, (hipStream_t)stream));
     return 0;
 }
 int bd_gemm_bf16(const void* a, int RB, const void* w, const void* bias, int N, int K, int S, int nw, float* scratch,
                  int* counters, void* out_bf16, void* stream) {
-    BD_TRY(bdk_gemm(a, RB, w, N, K, S, nw, BD_EPI_BF16, scratch, out_bf16, bias, counters, (hipStream_t)stream));
+    GemmCall g; g.A = a; g.RB = RB; g.W = w; g.N = N; g.K = K; g.S = S; g.nw = nw; g.epi = BD_EPI_BF16;
+    g.out_partial = scratch; g.out_act = out_bf16; g.bias = bias; g.cnt = counters;
+    BD_TRY(bdk_gemm_launch(g, (hipStream_t)stream));
     return 0;
 }
 int bd_gemm_f32(const void* a, int RB, const void* w, int N, int K, int S, int nw, float* scratch, int* counters, float* out_f32,
                 void* stream) {
-    BD_TRY(bdk_gemm(a, RB, w, N, K, S, nw, BD_EPI_F32, scratch, out_f32, nullptr, counters, (hipStream_t)stream));
+    GemmCall g; g.A = a; g.RB = RB; g.W = w; g.N = N; g.K = K; g.S = S; g.nw = nw; g.epi = BD_EPI_F32;
+    g.out_partial = scratch; g.out_act = out_f32; g.cnt = counters;
+    BD_TRY(bdk_gemm_launch(g, (hipStream_t)stream));
     return 0;
 }
 int bd_pack_weight8(void* dst, const void* src_fp8, int rows, int K, int dst_row0, int dst_rows_total, void* stream) {
@@ -428,8 +433,9 @@ int bd_gemm_w4a8(const void* a8, const float* ascale, int RB, const void* w4k, c
     if (K < 64 || K % 64) return unsupported("bd_gemm_w4a8: K must be a multiple of 64 (one exponent per 32 k, two per MFMA)");
     if (!a8 || !ascale || !w4k || !out) return fail("bd_gemm_w4a8: null operand");
     if (epi < 0 || epi > 3) return fail("bd_gemm_w4a8: epi 0 = fp32 slabs, 1 = SwiGLU, 2 = bf16(+bias), 3 = fp32 sum");
-    BD_TRY(bdk_gemm4a(a8, ascale, RB, w4k, wexp, N, K, S, nw, epi, epi == BD_EPI_PARTIAL ? (float*)out : scratch,
-                      epi == BD_EPI_PARTIAL ? nullptr : out, bias, counters, (hipStream_t)stream));
+    GemmCall g; g.A = a8; g.ascale = ascale; g.RB = RB; g.W = w4k; g.wexp = wexp; g.N = N; g.K = K; g.S = S; g.nw = nw; g.epi = epi;
+    g.out_partial = epi == BD_EPI_PARTIAL ? (float*)out : scratch; g.out_act = epi == BD_EPI_PARTIAL ? nullptr : out; g.bias = bias; g.cnt = counters;
+    BD_TRY(bdk_gemm_launch(g, (hipStream_t)stream));
     return 0;
 }
 /* standalone fp8 x fp8 GEMM (tests): a8 / ascale = fp8 activations in the A8 layout + per-row scales (bd_quant_rows8) */
@@ -437,8 +443,9 @@ int bd_gemm_w8a8(const void* a8, const float* ascale, int RB, const void* w8k, c
                  int epi, float* scratch, int* counters, void* out, void* stream) {
     if (!wscale || !ascale) return fail("bd_gemm_w8a8: scales required");
     if (epi < 0 || epi > 3) return fail("bd_gemm_w8a8: epi 0 = fp32 slabs, 1 = SwiGLU, 2 = bf16(+bias), 3 = fp32 sum");
-    BD_TRY(bdk_gemm8a(a8, ascale, RB, w8k, wscale, N, K, S, nw, epi, epi == BD_EPI_PARTIAL ? (float*)out : scratch,
-                      epi == BD_EPI_PARTIAL ? nullptr : out, bias, counters, (hipStream_t)stream));
+    GemmCall g; g.A = a8; g.ascale = ascale; g.RB = RB; g.W = w8k; g.wscale = wscale; g.N = N; g.K = K; g.S = S; g.nw = nw; g.epi = epi;
+    g.out_partial = epi == BD_EPI_PARTIAL ? (float*)out : scratch; g.out_act = epi == BD_EPI_PARTIAL ? nullptr : out; g.bias = bias; g.cnt = counters;
+    BD_TRY(bdk_gemm_launch(g, (hipStream_t)stream));
     return 0;
 }
 /* rows [M][K] fp32 -> fp8-e4m3 activations in the A8 layout + per-row scales (what the row kernels emit in wdtype 2) */
@@ -450,18 +457,22 @@ int bd_gemm_w8(const void* a, int RB, const void* w8, const float* wscale, const
                float* scratch, int* counters, void* out, void* stream) {
     if (!wscale) return fail("bd_gemm_w8: scales required");
     if (epi < 0 || epi > 3) return fail("bd_gemm_w8: epi 0 = fp32 slabs, 1 = SwiGLU, 2 = bf16(+bias), 3 = fp32 sum");
-    BD_TRY(bdk_gemm(a, RB, w8, N, K, S, nw, epi, epi == BD_EPI_PARTIAL ? (float*)out : scratch, epi == BD_EPI_PARTIAL ? nullptr : out,
-                    bias, counters, (hipStream_t)stream, wscale));
+    GemmCall g; g.A = a; g.RB = RB; g.W = w8; g.wscale = wscale; g.N = N; g.K = K; g.S = S; g.nw = nw; g.epi = epi;
+    g.out_partial = epi == BD_EPI_PARTIAL ? (float*)out : scratch; g.out_act = epi == BD_EPI_PARTIAL ? nullptr : out; g.bias = bias; g.cnt = counters;
+    BD_TRY(bdk_gemm_launch(g, (hipStream_t)stream));
     return 0;
 }
 int bd_gemm_swiglu(const void* a, int RB, const void* w, const void* bias, int N2, int K, int nw, void* act, void* stream) {
-    BD_TRY(bdk_gemm(a, RB, w, N2, K, 1, nw, BD_EPI_SWIGLU, nullptr, act, bias, nullptr, (hipStream_t)stream));
+    GemmCall g; g.A = a; g.RB = RB; g.W = w; g.N = N2; g.K = K; g.nw = nw; g.epi = BD_EPI_SWIGLU; g.out_act = act; g.bias = bias;
+    BD_TRY(bdk_gemm_launch(g, (hipStream_t)stream));
     return 0;
 }
 
 int bd_gemm_swiglu_splitk(const void* a, int RB, const void* w, const void* bias, int N2, int K, int S, int nw, float* scratch, int* counters,
                           void* act, void* stream) {
-    BD_TRY(bdk_gemm(a, RB, w, N2, K, S, nw, BD_EPI_SWIGLU, scratch, act, bias, counters, (hipStream_t)stream));
+    GemmCall g; g.A = a; g.RB = RB; g.W = w; g.N = N2; g.K = K; g.S = S; g.nw = nw; g.epi = BD_EPI_SWIGLU;
+    g.out_partial = scratch; g.out_act = act; g.bias = bias; g.cnt = counters;
+    BD_TRY(bdk_gemm_launch(g, (hipStream_t)stream));
     return 0;
 }
 
@@ -767,24 +778,32 @@ static WRef wref(const bd_ctx* c, const std::string& key, const char* ascale_ws 
     return r;
 }
 
-static int gemm(bd_ctx* c, const char* name, const void* A, int RB, WRef W, int N, int K, int S, int nw, int epi,
-                float* out, void* act, const void* bias, hipStream_t st) {
+static GemmCall gemm_call(bd_ctx* c, const void* A, int RB, WRef W, int N, int K, int S, int nw, int epi, float* out, void* act, const void* bias) {
+    GemmCall k; k.A = A; k.ascale = W.a; k.RB = RB; k.W = W.w; k.wscale = W.s; k.wexp = W.e; k.N = N; k.K = K; k.S = S; k.nw = nw;
+    k.epi = epi; k.out_partial = out; k.out_act = act; k.bias = bias;
+    k.cnt = (epi != BD_EPI_PARTIAL && S > 1) ? (int*)c->wptr("gemm.cnt") : nullptr;      // in-launch reduction tickets
+    return k;
+}
+static int gemm(bd_ctx* c, const char* name, const GemmCall& k, hipStream_t st) {
     bd_ctx::ProfRec r;
     if (c->prof_on) {
-        r.name = name; r.bytes = (double)N * K * (W.e ? 0.53125 : W.s ? 1 : 2);       // (MXFP4: 4 bits + one exponent byte per 32)
+        r.name = name; r.bytes = (double)k.N * k.K * (k.wexp ? 0.53125 : k.wscale ? 1 : 2);   // (MXFP4: 4 bits + one exponent byte per 32)
         hipEventCreate(&r.e0); hipEventCreate(&r.e1);
         hipEventRecord(r.e0, st);
     }
-    int* cnt = (epi != BD_EPI_PARTIAL && S > 1) ? (int*)c->wptr("gemm.cnt") : nullptr;   // in-launch reduction tickets
 #ifdef BD_GEMM_STAMP
     bdk_stamp_label(name);
 #endif
-    if (W.e && !W.a) return fail(std::string(name) + ": MXFP4 weights need an fp8 activation operand");
-    const int rc = W.e ? bdk_gemm4a(A, W.a, RB, W.w, W.e, N, K, S, nw, epi, out, act, bias, cnt, st)
-                 : W.a ? bdk_gemm8a(A, W.a, RB, W.w, W.s, N, K, S, nw, epi, out, act, bias, cnt, st)
-                       : bdk_gemm(A, RB, W.w, N, K, S, nw, epi, out, act, bias, cnt, st, W.s);
+    if (k.wexp && !k.ascale) return fail(std::string(name) + ": MXFP4 weights need an fp8 activation operand");
+    const int rc = bdk_gemm_launch(k, st);
     if (c->prof_on) { hipEventRecord(r.e1, st); c->prof.push_back(r); }
     return rc;
+}
+static int gemm(bd_ctx* c, const char* name, const void* A, int RB, WRef W, int N, int K, int S, int nw, int epi,
+                float* out, void* act, const void* bias, hipStream_t st, const BdHWait* wait = nullptr) {
+    GemmCall k = gemm_call(c, A, RB, W, N, K, S, nw, epi, out, act, bias);
+    if (wait && wait->flags) k.wait = wait;                  // (sp_wait; an empty one: the wait ran as a kernel of its own)
+    return gemm(c, name, k, st);
 }
 
 static Partial part(const bd_ctx* c, const std::string& ws, const void* bias, int S, int N, int Mpad) {
@@ -814,21 +833,19 @@ static int finalize_if_many(bd_ctx* c, Partial* q, const char* out_ws, int M, hi
 // workgroup (S x 64-128 KiB through one CU) costs more than it saves, so the slabs stay and the consumer sums them.
 static int linear(bd_ctx* c, const char* name, const void* A, int RB, WRef W, int N, int K, const GemmCfg& g,
                   const char* scratch_ws, const char* out_ws, const void* bias, int Mpad, Partial* res, hipStream_t st,
-                  bool force_reduce = false) {
+                  bool force_reduce = false, const BdHWait* wait = nullptr) {
     // 256-row passes run the 4-wave x 2-panel kernel, which has no in-launch reduction: slabs for the consumer there
     // (round 5: at 512 rows and more the 256-row kernel reduces TWO slices in the launch too -- the consumers stop reading fp32 slabs)
-    // -- for the wide weights of the 14B models on the 8-wave 256-row kernel, the forms measured; the ImageNet batches keep their rules)
     // (round 6, same box, 512 rows: slabs + finalize_rows 2339 us per evaluation against 2374 with the two slices reduced in the launch,
     //  even with the ticket-first form and the 16 B epilogues -- the reducing workgroup's tail (wait for the partner's drain, 256 KiB of
     //  write-through slab back through one CU, epilogue) is 17 us median against 6 for plain slabs, profiles/r06_launch_anatomy.log;
     //  "tune.reduce_max_s" = 2 selects the in-launch reduction there)
-    const bool wide_red = false && c->Mpad >= 512 && (double)N * K * 2 > 12e6 && (g.nw & 15) == 8 && g.kw == 1 && !c->wfp8;
-    const int max_s = (int)c->geti("tune.reduce_max_s", (c->Mpad % 256 == 0) ? (wide_red ? 2 : 0) : 2);
+    const int max_s = (int)c->geti("tune.reduce_max_s", (c->Mpad % 256 == 0) ? 0 : 2);
     if (g.S <= max_s || g.S == 1 || force_reduce) {            // a single slice needs no reduction: bias + rounding in the epilogue
-        BD_TRY(gemm(c, name, A, RB, W, N, K, g.S, g.code(), BD_EPI_BF16, (float*)c->wptr(scratch_ws), c->wptr(out_ws), bias, st));
+        BD_TRY(gemm(c, name, A, RB, W, N, K, g.S, g.code(), BD_EPI_BF16, (float*)c->wptr(scratch_ws), c->wptr(out_ws), bias, st, wait));
         *res = Partial{(const float*)c->ptr(out_ws), nullptr, 0, N, Mpad};
     } else {
-        BD_TRY(gemm(c, name, A, RB, W, N, K, g.S, g.code(), BD_EPI_PARTIAL, (float*)c->wptr(scratch_ws), nullptr, nullptr, st));
+        BD_TRY(gemm(c, name, A, RB, W, N, K, g.S, g.code(), BD_EPI_PARTIAL, (float*)c->wptr(scratch_ws), nullptr, nullptr, st, wait));
         *res = Partial{(const float*)c->ptr(scratch_ws), bias, g.S, N, Mpad};
     }
     return 0;
@@ -846,10 +863,12 @@ static int linear_rowsplit(bd_ctx* c, const char* name, const void* A, int RB, W
     // phase 1 of the exchange (every peer's slice of the partial into that peer's staging row) fused into the GEMM's epilogue where
     // the shape allows it: the exchange kernel then only signals, waits, reduces and pushes the result ("tune.tp_fuse" = 0: unfused)
     BdTpPush push;
-    const bool want = c->geti("tune.tp_fuse", 1) != 0 && bdk_tp_push_target(c->comm, rows, N, &push);
-    bdk_gemm_set_push(want ? &push : nullptr);
-    BD_TRY(gemm(c, name, A, RB, W, N, Klocal, g.S, g.code(), BD_EPI_F32, (float*)c->wptr(scratch_ws), c->wptr(tp_ws), nullptr, st));
-    if (bdk_gemm_push_used()) bdk_tp_mark_prepushed(c->comm);
+    GemmCall k = gemm_call(c, A, RB, W, N, Klocal, g.S, g.code(), BD_EPI_F32, (float*)c->wptr(scratch_ws), c->wptr(tp_ws), nullptr);
+    k.push = &push;
+    const bool fused = c->geti("tune.tp_fuse", 1) != 0 && bdk_tp_push_target(c->comm, rows, N, &push) && bdk_gemm_takes_push(k);
+    if (!fused) k.push = nullptr;
+    BD_TRY(gemm(c, name, k, st));
+    if (fused) bdk_tp_mark_prepushed(c->comm);
     BD_TRY(bdk_tp_allreduce(c->comm, (const float*)c->ptr(tp_ws), bias, rows, N, res, st));
     return 0;
 }
@@ -869,20 +888,20 @@ static int linear_rowsplit_sp(bd_ctx* c, const char* name, const void* A, int RB
     if (!bdk_tp_push_target_sp(c->comm, rows, N, c->geti("tune.sp_gsig", 0) ? *seq : 0, &push))
         return fail(std::string(name) + ": no sequence-parallel push target for this shape");
     if (push.done_cnt) push.done_cnt = (int*)c->wptr("gemm.cnt") + 16383;   // arrival counter in ordinary (L2-served) memory: the last counter word, never a tile's
-    bdk_gemm_set_push(&push);
-    BD_TRY(gemm(c, name, A, RB, W, N, Klocal, g.S, g.code(), BD_EPI_F32, (float*)c->wptr(scratch_ws), c->wptr(tp_ws), nullptr, st));
-    if (!bdk_gemm_push_used()) return fail(std::string(name) + ": the GEMM did not take the push target");
+    GemmCall k = gemm_call(c, A, RB, W, N, Klocal, g.S, g.code(), BD_EPI_F32, (float*)c->wptr(scratch_ws), c->wptr(tp_ws), nullptr);
+    k.push = &push;
+    if (!bdk_gemm_takes_push(k)) return fail(std::string(name) + ": the GEMM did not take the push target");
+    BD_TRY(gemm(c, name, k, st));
     bdk_comm_count_exchange(c->comm);
     return 0;
 }
-// the consumer GEMM of the operand rows pushed with sequence number `seq`: waits in its prologue ("tune.sp_wait" = 0: a one-workgroup
-// wait kernel in front of it instead)
-static int sp_arm_wait(bd_ctx* c, int seq, hipStream_t st) {
+// the wait of the consumer GEMM for the operand rows pushed with sequence number `seq`: *w for its prologue, handed to the linear() /
+// gemm() directly below ("tune.sp_wait" = 0: a one-workgroup wait kernel in front of it instead, *w stays empty)
+static int sp_wait(bd_ctx* c, int seq, BdHWait* w, hipStream_t st) {
+    *w = BdHWait{};
     if (c->geti("tune.sp_wait", 1) == 0) { BD_TRY(bdk_sp_wait_rows(c->comm, seq, c->M, st)); return 0; }
-    BdHWait w;
-    if (!bdk_sp_hwait(c->comm, seq, c->M, &w)) return fail("sequence-parallel exchange: no flag block");
-    w.inv = (int)c->geti("tune.sp_inv", 0);
-    bdk_gemm_set_hwait(&w);
+    if (!bdk_sp_hwait(c->comm, seq, c->M, w)) return fail("sequence-parallel exchange: no flag block");
+    w->inv = (int)c->geti("tune.sp_inv", 0);
     return 0;
 }
 
@@ -1010,9 +1029,10 @@ static int head_eval(bd_ctx* c, int i, hipStream_t st, int ada_buf = -1, bool x0
             if (l1.seq_h < 0) return fail("sequence-parallel exchange: more than 65535 hand-offs since the last bd_head_cond / bd_head_sample");
             BD_TRY(bdk_ln_mod_sp(l1, st));
             HeadAttnArgs at;
-            BD_TRY(sp_arm_wait(c, l1.seq_h, st));
+            BdHWait hw;
+            BD_TRY(sp_wait(c, l1.seq_h, &hw, st));
             BD_TRY(linear(c, "head.qkv", bdk_sp_hbuf(c->comm), RB, wref(c, pre + "wqkv"), 3 * Dl, D, gq, "head.qkv_part", "head.qkv_bf",
-                          c->ptr(pre + "bqkv"), Mp, &at.qkv, st));
+                          c->ptr(pre + "bqkv"), Mp, &at.qkv, st, false, &hw));
             BD_TRY(finalize_if_many(c, &at.qkv, "head.qkv_bf", M, st));
             at.o_frag = c->wptr("head.attn_frag"); at.nseq = M / c->Pn; at.dh = (int)c->geti("head.dh", 128); at.nhead = Dl / at.dh; at.D = Dl; at.RB = RB; at.P = c->Pn;
             BD_TRY(bdk_head_attn(at, st));
@@ -1024,13 +1044,13 @@ static int head_eval(bd_ctx* c, int i, hipStream_t st, int ada_buf = -1, bool x0
             l2.seq_h = bdk_sp_next_seq(c->comm);
             if (l2.seq_h < 0) return fail("sequence-parallel exchange: more than 65535 hand-offs since the last bd_head_cond / bd_head_sample");
             BD_TRY(bdk_ln_mod_sp(l2, st));
-            BD_TRY(sp_arm_wait(c, l2.seq_h, st));
+            BD_TRY(sp_wait(c, l2.seq_h, &hw, st));
             if (g1.S == 1 || c->geti("tune.w1_fused", g1.S > 2 ? 0 : 1)) {
                 BD_TRY(gemm(c, "head.w1", bdk_sp_hbuf(c->comm), RB, wref(c, pre + "w1"), 2 * Hl, D, g1.S, g1.code(), BD_EPI_SWIGLU,
-                            (float*)c->wptr("head.w1_part"), c->wptr("head.act_frag"), c->ptr(pre + "b1"), st));
+                            (float*)c->wptr("head.w1_part"), c->wptr("head.act_frag"), c->ptr(pre + "b1"), st, &hw));
             } else {                                           // many short K slices + a row-parallel SwiGLU pass over the slabs
                 BD_TRY(gemm(c, "head.w1", bdk_sp_hbuf(c->comm), RB, wref(c, pre + "w1"), 2 * Hl, D, g1.S, g1.code(), BD_EPI_PARTIAL,
-                            (float*)c->wptr("head.w1_part"), nullptr, nullptr, st));
+                            (float*)c->wptr("head.w1_part"), nullptr, nullptr, st, &hw));
                 SwigluArgs sw_;
                 sw_.up = part(c, "head.w1_part", c->ptr(pre + "b1"), g1.S, 2 * Hl, Mp);
                 sw_.act_frag = c->wptr("head.act_frag"); sw_.M = M; sw_.F = Hl; sw_.RB = RB; sw_.interleaved = 1;
@@ -1301,8 +1321,9 @@ static int llm_step_sp(bd_ctx* c, hipStream_t st) {
         if ((a1.seq_h = bdk_sp_next_seq(c->comm)) < 0) return fail(too_many);
         BD_TRY(bdk_rms_sp(a1, st));
         QkvPostArgs qa;
-        BD_TRY(sp_arm_wait(c, a1.seq_h, st));
-        BD_TRY(linear(c, "llm.qkv", bdk_sp_hbuf(c->comm), RB, wref(c, pre + "wqkv"), c->lNqkv, D, gq, "llm.qkv_part", "llm.qkv_bf", nullptr, Mp, &qa.qkv, st));
+        BdHWait hw;
+        BD_TRY(sp_wait(c, a1.seq_h, &hw, st));
+        BD_TRY(linear(c, "llm.qkv", bdk_sp_hbuf(c->comm), RB, wref(c, pre + "wqkv"), c->lNqkv, D, gq, "llm.qkv_part", "llm.qkv_bf", nullptr, Mp, &qa.qkv, st, false, &hw));
         qa.qn_w = c->ptr(pre + "q_norm"); qa.kn_w = c->ptr(pre + "k_norm");
         qa.cos = (const float*)c->ptr("llm.cos"); qa.sin = (const float*)c->ptr("llm.sin");
         qa.q_out = c->wptr("llm.q");
@@ -1322,9 +1343,9 @@ static int llm_step_sp(bd_ctx* c, hipStream_t st) {
         a2.part = (const float*)c->ptr("llm.tp_part"); a2.seq_p = seq_p;
         if ((a2.seq_h = bdk_sp_next_seq(c->comm)) < 0) return fail(too_many);
         BD_TRY(bdk_rms_sp(a2, st));
-        BD_TRY(sp_arm_wait(c, a2.seq_h, st));
+        BD_TRY(sp_wait(c, a2.seq_h, &hw, st));
         BD_TRY(gemm(c, "llm.gu", bdk_sp_hbuf(c->comm), RB, wref(c, pre + "wgu"), 2 * F, D, gg.S, gg.code(), BD_EPI_SWIGLU,
-                    (float*)c->wptr("llm.gu_part"), c->wptr("llm.act_frag"), nullptr, st));
+                    (float*)c->wptr("llm.gu_part"), c->wptr("llm.act_frag"), nullptr, st, &hw));
         BD_TRY(linear_rowsplit_sp(c, "llm.down", c->ptr("llm.act_frag"), RB, wref(c, pre + "wdown"), D, F, gd, "llm.br_part", "llm.tp_part", M, &seq_p, st));
     }
     if (!c->geti("rt.no_advance", 0)) {

@@ -448,24 +448,6 @@ static int g_wide_keep = -1;                              // weight loads of the
 static int g_wide_ring = 2, g_wide_xcd = -1;            // xcd: -1 = by shape (on when the weights outweigh the rows), 0 / 1 forced
 void bdk_gemm_tile_debug(int v);
 void bdk_gemm_half_form(int v);
-// tensor parallelism: the push target of the NEXT bdk_gemm call with the fp32-partial epilogue on the 128-row bf16 kernel (set by
-// bd_api.hip linear_rowsplit through bd_comm.hip bdk_tp_push_target; consumed and reported by bdk_gemm_push_used)
-static thread_local BdTpPush g_push;
-static thread_local bool g_push_set = false, g_push_used = false;
-void bdk_gemm_set_push(const BdTpPush* t) { g_push_set = t != nullptr; if (t) g_push = *t; g_push_used = false; }
-// sequence-parallel tensor parallelism: the NEXT bdk_gemm / bdk_gemm8 / bdk_gemm8a call on the 128-row kernel waits for its operand rows
-static thread_local BdHWait g_hwait;
-static thread_local bool g_hwait_set = false;
-void bdk_gemm_set_hwait(const BdHWait* w) { g_hwait_set = w != nullptr; if (w) g_hwait = *w; }
-bool bdk_gemm_take_hwait(BdHWait* out) { const bool s = g_hwait_set; if (s) *out = g_hwait; g_hwait_set = false; return s; }
-// the pending push target, if this launch can take it (fp32-partial epilogue of the 128-row kernel, whole 8-row groups per rank)
-bool bdk_gemm_claim_push(int epi, int RB, int N, BdTpPush* out) {
-    const bool ok = g_push_set && epi == BD_EPI_F32 && RB % 4 == 0 && RB < 8 && g_push.size > 1 && g_push.rows_per_rank % 8 == 0 && N % 32 == 0;
-    if (ok) { *out = g_push; g_push_used = true; }
-    g_push_set = false;
-    return ok;
-}
-bool bdk_gemm_push_used() { const bool u = g_push_used; g_push_used = false; g_push_set = false; return u; }
 static int g_red_first = 1;
 int bdk_red_first() { return g_red_first; }
 static int g_tile_minrb = 32;                            // row blocks from which the tiled kernel takes over ("tile.minrb": 16 = from 512 rows)
@@ -534,33 +516,33 @@ static int launch_gemm_wide(const GemmP& p0, int epi, hipStream_t st) {
     return xcd ? launch_gemm_wide_v<2, true>(p, epi, st) : launch_gemm_wide_v<2, false>(p, epi, st);
 }
 
-// `nw_ring` = waves per workgroup (2, 4, 8, 10) + 16 * ring + 256 * (kw - 1) + 2048 * pipe: ring in {0 (=2), 3, 4} = stages of
+// a launch takes its push target exactly here: fp32-partial epilogue of the 128-row bf16 / fp8-weight kernel, whole 8-row groups per rank
+bool bdk_gemm_takes_push(const GemmCall& c) {
+    return c.push && !c.ascale && !c.wexp && c.epi == BD_EPI_F32 && c.RB % 4 == 0 && c.RB < 8 && c.push->size > 1 &&
+           c.push->rows_per_rank % 8 == 0 && c.N % 32 == 0;
+}
+int bdk_gemm_launch(const GemmCall& c, hipStream_t st) {
+    return c.wexp ? bdk_gemm4a(c, st) : c.ascale ? bdk_gemm8a(c, st) : c.wscale ? bdk_gemm8(c, st) : bdk_gemm(c, st);
+}
+// GemmCall::nw = waves per workgroup (2, 4, 8, 10) + 16 * ring + 256 * (kw - 1) + 2048 * pipe + 4096 * half: ring in {0 (=2), 3, 4} = stages of
 // W/A a wave keeps in flight, kw in {1, 2} = waves that share one 32-column panel and split each K stage (NP = waves / kw
-// panels per tile), pipe = LDS reads one stage ahead of the MFMAs (falls back to the plain loop where not instantiated).
-int bdk_gemm(const void* A, int RB, const void* W, int N, int K, int S, int nw_ring, int epi,
-             float* out_partial, void* out_act, const void* bias, int* cnt, hipStream_t st, const float* wscale) {
-    if (wscale) return bdk_gemm8(A, RB, W, wscale, N, K, S, nw_ring, epi, out_partial, out_act, bias, cnt, st);   // fp8 weights: bd_gemm8.hip
-    // the armed push target / operand wait belong to THIS call whatever happens to it: taken (and cleared) before any early return, so a
-    // rejected shape cannot leave them attached to the next, unrelated GEMM of the thread
-    BdTpPush pend_push; const bool have_push = bdk_gemm_claim_push(epi, RB, N, &pend_push);
-    BdHWait pend_hw; const bool have_hw = bdk_gemm_take_hwait(&pend_hw);
-    const int nw = nw_ring & 15;
-    int ring = (nw_ring >> 4) & 15;
-    const int kw = ((nw_ring >> 8) & 3) + 1;
-    const bool pipe = (nw_ring >> 11) & 1;             // + 2048: software-pipelined LDS reads (4-wave workgroups, ring 2)
+// panels per tile), pipe = LDS reads one stage ahead of the MFMAs (falls back to the plain loop where not instantiated), half = the 256 x 128-tile kernel where it fits.
+int bdk_gemm(const GemmCall& c, hipStream_t st) {
+    const int RB = c.RB, N = c.N, K = c.K, S = c.S, epi = c.epi, nw = c.nw & 15, kw = ((c.nw >> 8) & 3) + 1;
+    int ring = (c.nw >> 4) & 15;
+    const bool pipe = (c.nw >> 11) & 1;                // + 2048: software-pipelined LDS reads (4-wave workgroups, ring 2)
     if (ring == 0) ring = 2;
     if (ring < 2 || ring > 4 || kw > 2 || nw % kw) return -7;
     const int np = nw / kw;
     // a ragged last tile (N/32 not a multiple of the panels per workgroup): the waves past the last panel repeat it and store nothing
     if (K % (64 * kw) || N % 32 || S < 1) return -2;
-    const int nst_total = K / (64 * kw), q = (nst_total + S - 1) / S;
-    if ((S - 1) * q >= nst_total) return -3;                       // an empty split
-    if (epi != BD_EPI_PARTIAL && S != 1 && (out_partial == nullptr || cnt == nullptr || (nw >= 9 && kw == 1))) return -4;   // needs slab scratch + counters
+    if (bd_gemm_empty_split(K / (64 * kw), S)) return -3;                       // an empty split
+    if (epi != BD_EPI_PARTIAL && S != 1 && (c.out_partial == nullptr || c.cnt == nullptr || (nw >= 9 && kw == 1))) return -4;   // needs slab scratch + counters
     size_t PS, SS;
     bdk_w_strides(N / 32, K, &PS, &SS);
-    GemmP p{(const u32x4*)A, (const u32x4*)W, out_partial, (bf16_t*)out_act, (const bf16_t*)bias, cnt, nullptr, RB, N, K, S, RB * 32, PS, SS};
-    if (have_push) p.push = pend_push;                 // the 128-row kernel's epilogue pushes the peers' slices itself (bd_gemm_kernel.h)
-    if (have_hw) { if (RB % 8 == 0 || pipe) return -10; p.hw = pend_hw; }     // (the 128-row plain-loop kernel only)
+    GemmP p{(const u32x4*)c.A, (const u32x4*)c.W, c.out_partial, (bf16_t*)c.out_act, (const bf16_t*)c.bias, c.cnt, nullptr, RB, N, K, S, RB * 32, PS, SS};
+    if (bdk_gemm_takes_push(c)) p.push = *c.push;      // the 128-row kernel's epilogue pushes the peers' slices itself (bd_gemm_kernel.h)
+    if (c.wait) { if (RB % 8 == 0 || pipe) return -10; p.hw = *c.wait; }      // (the 128-row plain-loop kernel only)
     // rows per pass over the weights: 256 (two images with CFG: W streamed once for both) when the row count allows,
     // else 128 / 64 / 32
     const int MB = (RB % 8 == 0 && nw >= 4 && kw == 1) ? 8 : ((RB % 4 == 0) ? 4 : RB);
@@ -571,10 +553,10 @@ int bdk_gemm(const void* A, int RB, const void* W, int N, int K, int S, int nw_r
     static const bool wide = [] { const char* e = getenv("BD_GEMM_WIDE"); return !(e && e[0] == '0'); }();
     // (a reduced epilogue -- S > 1 with bf16 / SwiGLU output -- exists for exactly two slices, round 5; more slices: the generic kernel)
     // 512 / 768 rows at ONE K slice with a rounded output (bd_api.hip choose_cfg "tune.half"): 256 x 128 tiles, split-K inside the workgroup
-    // (nw + 16: the caller asks for this kernel -- bd_api.hip GemmCfg::half; "half" = 2 routes every fitting shape, tests)
-    if (g_half && MB == 8 && nw == 8 && RB >= 16 && RB < g_tile_minrb && g_w_layout == 0 && N % 128 == 0 && K % 64 == 0 && !have_hw &&
+    // (nw + 4096: the caller asks for this kernel -- bd_api.hip GemmCfg::half; "half" = 2 routes every fitting shape, tests)
+    if (g_half && MB == 8 && nw == 8 && RB >= 16 && RB < g_tile_minrb && g_w_layout == 0 && N % 128 == 0 && K % 64 == 0 &&
         ((S == 1 && (epi == BD_EPI_BF16 || epi == BD_EPI_SWIGLU)) || epi == BD_EPI_PARTIAL) && (K / 64) / S >= 2 &&
-        (g_half == 2 || ((nw_ring >> 12) & 1)))
+        (g_half == 2 || ((c.nw >> 12) & 1)))
         return bdk_gemm_half(p, epi, st);
     if (wide && MB == 8 && nw == 8 && N % 256 == 0 && epi != BD_EPI_F32 && !(S > 1 && epi != BD_EPI_PARTIAL && (S != 2 || RB < 16))) {
         // >= 512 rows: the matrix pipe is the roofline -> both operands through LDS, 256 x 256 tiles (bd_gemm_tile.hip)

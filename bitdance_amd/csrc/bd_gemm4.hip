@@ -55,22 +55,17 @@ int bdk_pack_w4k(void* dst, void* dst_e, const void* src, const void* src_e, con
 
 // MXFP4 weights x fp8 activations (A: the A8 layout + `ascale` [rows] fp32; `wexp`: the packed exponent stream): the launch forms of
 // bdk_gemm8a, instance for instance
-int bdk_gemm4a(const void* A8, const float* ascale, int RB, const void* W4k, const void* wexp, int N, int K, int S, int nw_ring, int epi,
-               float* out_partial, void* out_act, const void* bias, int* cnt, hipStream_t st) {
-    // (armed push target / operand wait: taken before any early return, bdk_gemm.  The sequence-parallel hand-off carries bf16 rows only)
-    { BdTpPush none_p; (void)bdk_gemm_claim_push(-1, RB, N, &none_p); }
-    { BdHWait none; if (bdk_gemm_take_hwait(&none)) return -10; }
-    const int nw = nw_ring & 15;
-    const int kw = ((nw_ring >> 8) & 3) + 1;
-    if (kw > 2 || nw == 0 || nw % kw || !ascale || !wexp || !A8 || !W4k) return -7;
+int bdk_gemm4a(const GemmCall& c, hipStream_t st) {
+    if (c.wait) return -10;                                  // (the sequence-parallel hand-off carries bf16 rows only)
+    const int RB = c.RB, N = c.N, K = c.K, S = c.S, epi = c.epi, nw = c.nw & 15, kw = ((c.nw >> 8) & 3) + 1;
+    if (kw > 2 || nw == 0 || nw % kw || !c.ascale || !c.wexp || !c.A || !c.W) return -7;
     const int np = nw / kw;
     if (K < 64 || K % (64 * kw) || N < 32 || N % (32 * np) || S < 1 || RB < 1) return -2;
-    const int nst_total = K / (64 * kw), q = (nst_total + S - 1) / S;
-    if ((S - 1) * q >= nst_total) return -3;
-    if (epi != BD_EPI_PARTIAL && S != 1 && (out_partial == nullptr || cnt == nullptr)) return -4;
+    if (bd_gemm_empty_split(K / (64 * kw), S)) return -3;
+    if (epi != BD_EPI_PARTIAL && S != 1 && (c.out_partial == nullptr || c.cnt == nullptr)) return -4;
     const size_t PS = (size_t)(K >> 6) * 64, SS = 64;        // 16 B units: panel stride, 64-deep stage stride (one load per lane)
-    GemmP p{(const u32x4*)A8, (const u32x4*)W4k, out_partial, (bf16_t*)out_act, (const bf16_t*)bias, cnt, (const float*)wexp, RB, N, K, S, RB * 32, PS, SS};
-    p.ascale = ascale;
+    GemmP p{(const u32x4*)c.A, (const u32x4*)c.W, c.out_partial, (bf16_t*)c.out_act, (const bf16_t*)c.bias, c.cnt, (const float*)c.wexp, RB, N, K, S, RB * 32, PS, SS};
+    p.ascale = c.ascale;
     const int MB = (RB % 8 == 0 && kw == 1 && np == 4 && S == 1 && epi == BD_EPI_BF16) ? 8 : ((RB % 4 == 0) ? 4 : RB);   // (256-row passes: bdk_gemm8a)
     if (MB != 8 && MB != 4 && MB != 2 && MB != 1) return -5;
     // ring 4 as in bdk_gemm8a: a stage is 1 KiB + 256 B per wave, the loop is bound by bytes in flight

@@ -66,22 +66,17 @@ int bdk_pack_w8k(void* dst, const void* src, const void* src2, int panels, int K
 }
 
 // fp8 weights AND fp8 activations (A: the A8 layout + `ascale` [rows] fp32): the launch forms of the 128-row kernel
-int bdk_gemm8a(const void* A8, const float* ascale, int RB, const void* W8k, const float* wscale, int N, int K, int S, int nw_ring, int epi,
-               float* out_partial, void* out_act, const void* bias, int* cnt, hipStream_t st) {
-    // (armed push target / operand wait: taken before any early return, bdk_gemm.  The sequence-parallel hand-off carries bf16 rows only)
-    { BdTpPush none_p; (void)bdk_gemm_claim_push(-1, RB, N, &none_p); }
-    { BdHWait none; if (bdk_gemm_take_hwait(&none)) return -10; }
-    const int nw = nw_ring & 15;
-    const int kw = ((nw_ring >> 8) & 3) + 1;
-    if (kw > 2 || nw % kw || !ascale || !wscale) return -7;
+int bdk_gemm8a(const GemmCall& c, hipStream_t st) {
+    if (c.wait) return -10;                                  // (the sequence-parallel hand-off carries bf16 rows only)
+    const int RB = c.RB, N = c.N, K = c.K, S = c.S, epi = c.epi, nw = c.nw & 15, kw = ((c.nw >> 8) & 3) + 1;
+    if (kw > 2 || nw % kw || !c.ascale || !c.wscale) return -7;
     const int np = nw / kw;
     if (K % (64 * kw) || N % (32 * np) || S < 1) return -2;
-    const int nst_total = K / (64 * kw), q = (nst_total + S - 1) / S;
-    if ((S - 1) * q >= nst_total) return -3;
-    if (epi != BD_EPI_PARTIAL && S != 1 && (out_partial == nullptr || cnt == nullptr)) return -4;
+    if (bd_gemm_empty_split(K / (64 * kw), S)) return -3;
+    if (epi != BD_EPI_PARTIAL && S != 1 && (c.out_partial == nullptr || c.cnt == nullptr)) return -4;
     const size_t PS = (size_t)(K >> 6) * 128, SS = 128;
-    GemmP p{(const u32x4*)A8, (const u32x4*)W8k, out_partial, (bf16_t*)out_act, (const bf16_t*)bias, cnt, wscale, RB, N, K, S, RB * 32, PS, SS};
-    p.ascale = ascale;
+    GemmP p{(const u32x4*)c.A, (const u32x4*)c.W, c.out_partial, (bf16_t*)c.out_act, (const bf16_t*)c.bias, c.cnt, c.wscale, RB, N, K, S, RB * 32, PS, SS};
+    p.ascale = c.ascale;
     // 256-row passes (the adaLN projection of a group of evaluations, bd_api.hip head_ada_group): one pass over the weights per 256
     // rows, same MFMA and K order per row as the 128-row form -> bit-identical rows.  Only that call shape (one slice, bf16 epilogue):
     // everything else keeps the 128-row forms the parity tests cover
@@ -98,25 +93,19 @@ int bdk_gemm8a(const void* A8, const float* ascale, int RB, const void* W8k, con
     return -6;
 }
 
-int bdk_gemm8(const void* A, int RB, const void* W8, const float* wscale, int N, int K, int S, int nw_ring, int epi,
-              float* out_partial, void* out_act, const void* bias, int* cnt, hipStream_t st) {
-    // the armed push target / operand wait belong to THIS call: taken (and cleared) before any early return (bdk_gemm)
-    BdTpPush pend_push; const bool have_push = bdk_gemm_claim_push(epi, RB, N, &pend_push);   // tensor parallelism: the fp32-partial epilogue pushes the peers' rows
-    BdHWait pend_hw; const bool have_hw = bdk_gemm_take_hwait(&pend_hw);                      // sequence-parallel: the operand comes from the peers' row kernels
-    const int nw = nw_ring & 15;
-    const int kw = ((nw_ring >> 8) & 3) + 1;
+int bdk_gemm8(const GemmCall& c, hipStream_t st) {
+    const int RB = c.RB, N = c.N, K = c.K, S = c.S, epi = c.epi, nw = c.nw & 15, kw = ((c.nw >> 8) & 3) + 1;
     if (kw > 2 || nw % kw) return -7;
     const int np = nw / kw;
     if (K % (64 * kw) || N % (32 * np) || S < 1) return -2;
-    const int nst_total = K / (64 * kw), q = (nst_total + S - 1) / S;
-    if ((S - 1) * q >= nst_total) return -3;
-    if (epi != BD_EPI_PARTIAL && S != 1 && (out_partial == nullptr || cnt == nullptr || (nw == 10 && kw == 1))) return -4;
+    if (bd_gemm_empty_split(K / (64 * kw), S)) return -3;
+    if (epi != BD_EPI_PARTIAL && S != 1 && (c.out_partial == nullptr || c.cnt == nullptr || (nw == 10 && kw == 1))) return -4;
     const size_t PS = (size_t)(K >> 5) * 64, SS = 128;        // 16 B units: panel stride, 64-deep stage stride
-    GemmP p{(const u32x4*)A, (const u32x4*)W8, out_partial, (bf16_t*)out_act, (const bf16_t*)bias, cnt, wscale, RB, N, K, S, RB * 32, PS, SS};
+    GemmP p{(const u32x4*)c.A, (const u32x4*)c.W, c.out_partial, (bf16_t*)c.out_act, (const bf16_t*)c.bias, c.cnt, c.wscale, RB, N, K, S, RB * 32, PS, SS};
     const int MB = (RB % 4 == 0) ? 4 : RB;                     // 128-row passes (row blocks beyond 4: grid.y)
     if (MB != 4 && MB != 2 && MB != 1) return -5;
-    if (have_push) p.push = pend_push;
-    if (have_hw) p.hw = pend_hw;
+    if (bdk_gemm_takes_push(c)) p.push = *c.push;           // tensor parallelism: the fp32-partial epilogue pushes the peers' rows
+    if (c.wait) p.hw = *c.wait;                              // sequence-parallel: the operand comes from the peers' row kernels
     // ring 2 (two 2 KiB stages per wave in flight).  Ring 4 was measured SLOWER (adaLN 125 vs 97 us, profiles/r02_bench_fp8_v2.json):
     // at 128 rows and half the bytes per weight the workgroup is bound by its LDS-read + MFMA work per stage (256 FLOP per weight
     // byte, at the ridge), not by bytes in flight.

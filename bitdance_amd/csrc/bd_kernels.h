@@ -29,19 +29,35 @@ static inline bool bd_lds_optin(const void* fn, int bytes, unsigned long long* d
 
 struct BdStepState;
 
-// ---- bd_gemm.hip
-// wscale != nullptr: W holds fp8-e4m3 weights (bdk_pack_w8) with per-packed-row fp32 scales
-int bdk_gemm(const void* A, int RB, const void* W, int N, int K, int S, int nw, int epi,
-             float* out_partial, void* out_act, const void* bias, int* tile_counters, hipStream_t st, const float* wscale = nullptr);
-// ---- bd_gemm8.hip : the same GEMM on fp8-e4m3 weights
-int bdk_gemm8(const void* A, int RB, const void* W8, const float* wscale, int N, int K, int S, int nw, int epi,
-              float* out_partial, void* out_act, const void* bias, int* tile_counters, hipStream_t st);
-// fp8 weights + fp8 activations on the fp8 matrix pipe (bd_gemm_kernel.h WT = 2)
-int bdk_gemm8a(const void* A8, const float* ascale, int RB, const void* W8k, const float* wscale, int N, int K, int S, int nw, int epi,
-               float* out_partial, void* out_act, const void* bias, int* tile_counters, hipStream_t st);
-// MXFP4 weights + fp8 activations on the same pipe (bd_gemm_kernel.h WT = 3, bd_gemm4.hip); wexp: the packed E8M0 exponent stream
-int bdk_gemm4a(const void* A8, const float* ascale, int RB, const void* W4k, const void* wexp, int N, int K, int S, int nw, int epi,
-               float* out_partial, void* out_act, const void* bias, int* tile_counters, hipStream_t st);
+// ---- bd_gemm.hip : one weight-streaming GEMM launch.  The weight format selects the launcher (bdk_gemm_launch): wexp -> bdk_gemm4a,
+// ascale -> bdk_gemm8a, wscale -> bdk_gemm8, else the bf16 kernels of bdk_gemm
+struct BdTpPush; struct BdHWait;
+struct GemmCall {
+    const void* A = nullptr;          // activations, fragment-major bf16; or fp8 in the A8 layout with
+    const float* ascale = nullptr;    //   their per-row fp32 scales (bd_gemm_kernel.h WT = 2 / 3)
+    const void* W = nullptr;          // packed weights: bf16 (bdk_pack_w); or fp8-e4m3 (bdk_pack_w8 / bdk_pack_w8k) with
+    const float* wscale = nullptr;    //   their per-packed-row fp32 scales; or MXFP4 (bdk_pack_w4k) with
+    const void* wexp = nullptr;       //   the packed E8M0 exponent stream
+    int RB = 0, N = 0, K = 0, S = 1;  // 32-row blocks, output columns, depth, K slices
+    int nw = 0;                       // waves + 16 * ring + 256 * (kw - 1) + 2048 * pipe + 4096 * half (bd_gemm.hip bdk_gemm)
+    int epi = BD_EPI_PARTIAL;
+    float* out_partial = nullptr;     // split-K slabs (BD_EPI_PARTIAL) / slab scratch of the in-launch reduction
+    void* out_act = nullptr;          // the output of every other epilogue
+    const void* bias = nullptr; int* cnt = nullptr;   // cnt: tickets of the in-launch reduction
+    // tensor parallelism.  push: the fp32-partial epilogue writes the peers' rows into their staging buffers -- honoured exactly when
+    // bdk_gemm_takes_push(), dropped otherwise.  wait: the prologue waits for operand rows the peers push -- the 128-row plain-loop
+    // kernels of bdk_gemm / bdk_gemm8 only, every other form returns -10 before it launches (so the half / tiled / 256-row routes
+    // never see one).  Both belong to this launch alone; a rejected call leaves nothing behind.
+    const BdTpPush* push = nullptr; const BdHWait* wait = nullptr;
+};
+bool bdk_gemm_takes_push(const GemmCall& c);
+// `stages` 64 * kw-deep K stages in S slices of ceil(stages / S): true when the last slice would be empty (the launchers' -3)
+static inline bool bd_gemm_empty_split(int stages, int S) { const int q = (stages + S - 1) / S; return (S - 1) * q >= stages; }
+int bdk_gemm_launch(const GemmCall& c, hipStream_t st);
+int bdk_gemm(const GemmCall& c, hipStream_t st);
+int bdk_gemm8(const GemmCall& c, hipStream_t st);     // bd_gemm8.hip: fp8-e4m3 weights, bf16 activations
+int bdk_gemm8a(const GemmCall& c, hipStream_t st);    // fp8 weights + fp8 activations on the fp8 matrix pipe
+int bdk_gemm4a(const GemmCall& c, hipStream_t st);    // bd_gemm4.hip: MXFP4 weights + fp8 activations on the same pipe
 int bdk_pack_w4k(void* dst, void* dst_e, const void* src, const void* src_e, const void* src2, const void* src2_e, int panels, int K, int nb0,
                  int panels_total, int mode, hipStream_t st);
 int bdk_pack_w8k(void* dst, const void* src_fp8, const void* src2_fp8, int panels, int K, int nb0, int panels_total, int mode, hipStream_t st);
@@ -342,8 +358,6 @@ int bdk_sp_wait_rows(bd_comm* c, int seq, int rows, hipStream_t st);   // the wa
 int bdk_sp_selftest(bd_comm* c, int round, int rows, int D, int wait_in_check, int* bad_dev, hipStream_t st);   // bd_sp.hip
 long long bdk_sp_hbuf_bytes(const bd_comm* c);
 void* bdk_sp_hbuf(const bd_comm* c);
-void bdk_gemm_set_hwait(const BdHWait* w);              // bd_gemm.hip: the NEXT bdk_gemm / bdk_gemm8 call waits in its prologue
-bool bdk_gemm_take_hwait(BdHWait* out);
 void bdk_comm_count_exchange(bd_comm* c);
 
 struct LnModSpArgs {           // ln_mod for this rank's rows only, fed by the peers' partial pushes, feeding every rank's operand buffer
@@ -400,9 +414,6 @@ int bdk_tok_finish(const TokFinishArgs& a, hipStream_t st);
 bool bdk_tp_push_target(bd_comm* c, int rows, int N, BdTpPush* out);
 bool bdk_tp_push_target_sp(bd_comm* c, int rows, int N, int seq, BdTpPush* out);   // seq > 0: the GEMM's last workgroup signals the owners
 void bdk_tp_mark_prepushed(bd_comm* c);
-void bdk_gemm_set_push(const BdTpPush* t);      // bd_gemm.hip
-bool bdk_gemm_push_used();
-bool bdk_gemm_claim_push(int epi, int RB, int N, BdTpPush* out);
 
 // ---- bd_attn.hip
 struct HeadAttnArgs {       // DiT attention over one patch (seq = P = 64 or 16), non-causal      flow_head:192-220
