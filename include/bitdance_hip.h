@@ -166,6 +166,56 @@ int bd_llm_attn(const void* q, const void* k_cache, const void* vt_cache, const 
 int bd_in_attn(const void* q, const void* k_cache, const void* v_cache, int kv_len, int nseq, int P, int nh, int Lmax, int causal,
                void* state, void* o_frag, int row_blocks, void* stream);
 
+/* ---- the row kernels and the DiT head attention standalone (tests): a thin wrapper per launcher of csrc/bd_rows.hip / bd_attn.hip that
+ *      fills the launcher's argument struct and calls it on caller buffers, so the launcher picks the kernel form exactly as in the
+ *      engine.  Every call validates on the host first and returns BD_ERR_UNSUPPORTED (text in bd_last_error()) before anything is
+ *      launched: dimension multiples, row_blocks * 32 >= rows, kv_len + P <= Lmax and the table sizes, C <= 32, nseq <= 64, offsets
+ *      inside the adaLN row.  Conventions:
+ *      - a Linear output ("pend", "qkv", "up") is (pointer, bias, S, rows): S >= 1 split-K slabs [S][rows][N] fp32 (+ optional bf16
+ *        bias[N]), S == 0 a finished bf16 [rows][N] tensor (no bias), S < 0 none (where the kernel allows that);
+ *      - fragment-major outputs cover row_blocks * 32 rows (layout above); with a8_scale != NULL the output is the fp8-e4m3 operand
+ *        (A8 layout) and a8_scale receives one fp32 scale per row;
+ *      - `state` is a device BdStepState (65 int32) that the call fills with `step` / kv_len[] by a kernel on `stream`.
+ *      bd_ln_mod: x (+= bf16(branch) * gate); h = LN(x) * (1 + scale) + shift.  wave_rows 1: the wave-per-row form (bf16 output, D <= 1024).
+ *      bd_rms: Qwen3 RMSNorm on the fp32 (bf16_stream 1: bf16) residual stream R [rows][D]; cond_frag = bf16(normed + pos[step * P + m % P]).
+ *      bd_qkv_post: q / k head RMSNorm, RoPE (tables [maxpos][128] fp32) and the K [seq][nkv][Lmax][128] / V^T [seq][nkv][128][Lmax] append
+ *      at kv_len[seq] + p; qkv [nseq * P][(nh + 2 nkv) * 128].
+ *      bd_head_attn: qkv [nseq * P][3 * nhead * dh]; P = 64 (dh 128), or P <= 16 (dh 128 / 64): the matrix-pipe form exactly for P = 16
+ *      with a finished bf16 qkv (S = 0), the element-wise form otherwise.
+ *      bd_head_final: final LN-mod, Linear(D -> C), [2 sigmoid - 1], one sampler step on xt [BP][C].  scalars7 = {t, dt, den, var, 1 - t,
+ *      noise_scale, cfg} (host memory); noise [noise_steps][noise_evals][BP][C]; rows: cond bp, uncond BP + bp (cfg_mult 2).
+ *      bd_swiglu_rows: act = silu(gate) * up from `up` [rows][2 F]; interleaved 1: packed (16 gate | 16 up) columns, 0: [gate F | up F].
+ *      bd_in_rms / bd_in_qkv_post: the ImageNet transformer's nn.RMSNorm (fp32 weight) and interleaved-pair RoPE (rope [rows][32][2]) with
+ *      the K / V [seq][nh][Lmax][64] append, one kv_len for every sequence; q comes out multiplied by 64^-0.5.
+ *      bd_head_y_all: y_i = silu(temb[i] + cemb) for n_evals evaluations, G per adaLN GEMM operand (G > 1: row_blocks * G % 8 == 0);
+ *      a short last group's pad rows and scales are zero-filled. */
+int bd_ln_mod(void* X, const void* pend, const void* pend_bias, int pend_S, int pend_rows, const void* ada, int ada_ld, int gate_off,
+              int scale_off, int shift_off, const float* ln_w, const float* ln_b, void* h_frag, float* a8_scale, int M, int D,
+              int row_blocks, float eps, int wave_rows, void* stream);
+int bd_rms(float* R, const void* pend, const void* pend_bias, int pend_S, int pend_rows, const void* w, void* a_frag, float* a8_scale,
+           float* hidden_out, void* cond_frag, const float* pos, int pos_rows, int step, void* state, int M, int D, int P, int row_blocks,
+           float eps, int bf16_stream, void* stream);
+int bd_qkv_post(const void* qkv, const void* qkv_bias, int qkv_S, int qkv_rows, const void* qn_w, const void* kn_w, const float* cos,
+                const float* sin, int maxpos, void* q_out, void* k_cache, void* vt_cache, const int* kv_len, int nseq, int P, int nh,
+                int nkv, int Lmax, float eps, int rope_bf16, void* state, void* stream);
+int bd_head_attn(const void* qkv, const void* qkv_bias, int qkv_S, int qkv_rows, void* o_frag, int nseq, int nhead, int P, int dh,
+                 int row_blocks, void* stream);
+int bd_head_final(const void* X, const void* pend, const void* pend_bias, int pend_S, int pend_rows, const void* ada, int ada_ld,
+                  int gate_off, int scale_off, int shift_off, const void* lin_w, const void* lin_b, float* xt, const float* noise,
+                  int noise_evals, int noise_steps, int eval_index, int step, void* state, float* pred_out, float* tok_cur, float* tok_all,
+                  int T, int P, float* xhat_out, const float* scalars7, int is_final, int cfg_mult, int BP, int D, int C, float eps_ln,
+                  int sigmoid, const float* cfg_table, int cfg_table_len, int tok_branches, void* X_next, const void* in_w, const void* in_b,
+                  void* stream);
+int bd_swiglu_rows(const void* up, const void* up_bias, int up_S, int up_rows, void* act_frag, int M, int F, int row_blocks,
+                   int interleaved, void* stream);
+int bd_in_rms(float* R, const void* pend, const void* pend_bias, int pend_S, int pend_rows, int init_from_pend, int renorm_to_R,
+              const float* w, void* a_frag, float* hidden_out, void* cond_frag, const float* pos, int pos_rows, int step, void* state,
+              int M, int D, int P, int row_blocks, float eps, int f32_stream, void* stream);
+int bd_in_qkv_post(const void* qkv, const void* qkv_bias, int qkv_S, int qkv_rows, const float* rope, int rope_rows, void* q_out,
+                   void* k_cache, void* v_cache, int kv_len, int nseq, int P, int nh, int Lmax, void* state, void* stream);
+int bd_head_y_all(const void* cemb, const void* temb, void* y_all, float* a8_scale, int M, int D, int row_blocks, int n_evals, int G,
+                  void* stream);
+
 /* ---- tensor parallelism over xGMI (no counterpart in the reference, whose multi-GPU mode is replicas,
  *      eval/eval_dpg.py:25-29).  One bd_comm per process/GPU.  bd_comm_create allocates (once, not on the hot path) the
  *      exported staging/result buffer for exchanges of up to max_elems = rows*N elements and an uncached flag block;

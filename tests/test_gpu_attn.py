@@ -29,6 +29,8 @@ import math
 import pytest
 import torch
 
+from tests.rows_ref import unfrag
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -47,11 +49,6 @@ def _lib():
 
 def _stream():
     return torch.cuda.current_stream().cuda_stream
-
-
-def unfrag(buf: torch.Tensor, rb: int, width: int) -> torch.Tensor:
-    """Fragment-major bf16 [width / 16][rb][2][32][8] -> row-major [rb * 32][width] (as test_gemm_swiglu un-fragments)."""
-    return buf.view(width // 16, rb, 2, 32, 8).permute(1, 3, 0, 2, 4).reshape(rb * 32, width)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
