@@ -428,6 +428,7 @@ extern "C" {
 int bd_conv_strided(const void* in, const void* w_packed, const void* bias, const void* res, int res_f32, void* out, int out_mode, int out_f32,
                     int n, int H, int W, int Cin, int Cout, int taps, int stride, void* stream) {
     if (stride != 1 && !(stride == 2 && taps == 9)) return bd_unsupported("bd_conv_strided: stride 1, or 2 with a 3x3 kernel");
+    if (n < 1) return bd_unsupported("bd_conv: n >= 1");
     int TW = 32;
     {
         long long best = -1;
@@ -437,7 +438,7 @@ int bd_conv_strided(const void* in, const void* w_packed, const void* bias, cons
             if (best < 0 || area < best) { best = area; TW = tw; }
         }
     }
-    if ((taps != 9 && taps != 1) || Cin % 32 || (Cout % 8 && out_mode != 2) || H < 1 || W < 1 || out_mode < 0 || out_mode > 3 ||
+    if ((taps != 9 && taps != 1) || Cin < 32 || Cin % 32 || Cout < 1 || (Cout % 8 && out_mode != 2) || H < 1 || W < 1 || out_mode < 0 || out_mode > 3 ||
         (out_mode == 1 && (Cout % 4 || (Cout / 4) % 8)))
         return bd_unsupported("bd_conv: taps 9 / 1, Cin % 32, Cout % 8 (any Cout for the image output), depth-to-space needs Cout / 4 % 8 == 0");
     ConvP p;
@@ -462,6 +463,7 @@ int bd_conv(const void* in, const void* w_packed, const void* bias, const void* 
 /* GroupNorm(32) statistics of an unpadded NHWC tensor -> stats [n][32][2] = (mean, rstd); partial: scratch [n][ceil(HW / 256)][32][2] fp32 */
 int bd_gn_stats(const void* x, int x_f32, float* partial, float* stats, int n, int HW, int C, float eps, void* stream) {
     if (C % 32 || C < 32 || C > 2048 || (256 % (C / 8)) != 0) return bd_unsupported("bd_gn_stats: C must be a power-of-two multiple of 32, <= 2048");
+    if (n < 1 || HW < 1) return bd_unsupported("bd_gn_stats: n, HW >= 1");
     GnStatsP p{x, x_f32, partial, n, HW, C, (HW + 255) / 256};
     BD_LAUNCH(gn_stats_kernel, dim3(p.chunks, n), dim3(256), 0, (hipStream_t)stream, p);
     GnFinalP f{partial, stats, n, HW, C, p.chunks, eps};
@@ -471,7 +473,9 @@ int bd_gn_stats(const void* x, int x_f32, float* partial, float* stats, int n, i
 
 int bd_gn_apply(const void* x, int x_f32, const float* stats, const float* gamma, const float* beta, const float* scale, const float* bias,
                 void* out, int out_mode, int swish, int n, int H, int W, int C, void* stream) {
-    if (C % 32) return bd_unsupported("bd_gn_apply: C % 32");
+    if (C < 32 || C % 32) return bd_unsupported("bd_gn_apply: C % 32");
+    if (out_mode < 0 || out_mode > 2) return bd_unsupported("bd_gn_apply: out_mode 0 (padded bf16), 1 (fp32) or 2 (bf16)");
+    if (n < 1 || H < 1 || W < 1) return bd_unsupported("bd_gn_apply: n, H, W >= 1");
     GnApplyP p{x, x_f32, stats, gamma, beta, scale, bias, out, out_mode, swish, n, H, W, C};
     if ((C / 8) < 256 ? (256 % (C / 8)) != 0 : ((C / 8) % 256) != 0) return bd_unsupported("bd_gn_apply: C / 8 must divide, or be a multiple of, 256");
     BD_LAUNCH(gn_apply_kernel, dim3(n * H), dim3(256), 0, (hipStream_t)stream, p);
@@ -479,6 +483,7 @@ int bd_gn_apply(const void* x, int x_f32, const float* stats, const float* gamma
 }
 
 int bd_tokens_to_padded(const float* z, void* out, int n, int C, int H, int W, void* stream) {
+    if (n < 1 || C < 1 || H < 1 || W < 1) return bd_unsupported("bd_tokens_to_padded: n, C, H, W >= 1");
     const size_t total = (size_t)n * C * H * W;
     const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
     BD_LAUNCH(tokens_to_padded_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, z, (bf16_t*)out, n, C, H, W);

@@ -295,7 +295,12 @@ int bd_gfq_codes(const int* idx, float* codes, int ntok, int ncodebooks, int bit
  *      bd_conv: 3x3 (taps 9, padded input) or 1x1 (taps 1, unpadded input) as an implicit GEMM on the matrix pipe; w_packed =
  *      bd_pack_weight of the [Cout rounded up to 256][taps * Cin] matrix with K ordered (ky, kx, ci); conv output = bf16(acc + bias)
  *      (F.conv2d under bf16 autocast), then out_mode 0: unpadded NHWC (+ residual fp32 / bf16 -> fp32 / bf16), 1: depth-to-space
- *      (autoencoder.py:198-230, DCR) bf16 NHWC [n][2H][2W][Cout/4], 2: fp32 NCHW image, 3: padded bf16 NHWC. */
+ *      (autoencoder.py:198-230, DCR) bf16 NHWC [n][2H][2W][Cout/4], 2: fp32 NCHW image, 3: padded bf16 NHWC.
+ *      Every entry of this group validates on the host and returns BD_ERR_UNSUPPORTED before anything is launched: the convolution
+ *      for taps outside {1, 9}, Cin < 32 or Cin % 32, Cout < 1 or Cout % 8 (any Cout >= 1 for out_mode 2), out_mode 1 with Cout / 4 % 8, out_mode outside 0 .. 3,
+ *      a stride other than 1 or (2 with taps 9), n, H or W < 1; bd_gn_stats for C not a power-of-two multiple of 32 or > 2048, n or
+ *      HW < 1; bd_gn_apply for C < 32, C % 32, C / 8 neither a divisor nor a multiple of 256, out_mode outside 0 .. 2, n, H or W < 1;
+ *      bd_tokens_to_padded for n, C, H or W < 1. */
 int bd_conv(const void* in, const void* w_packed, const void* bias_bf16, const void* res, int res_f32, void* out, int out_mode, int out_f32,
             int n, int H, int W, int Cin, int Cout, int taps, void* stream);
 /* the same with a stride: 1, or 2 for a 3x3 / padding-1 kernel -- the Encoder's down-sampling convolution (autoencoder.py:59-127:
