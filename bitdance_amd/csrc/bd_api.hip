@@ -49,12 +49,6 @@ int anatomy_get(int i, char* name64, long long* off_words, int* nwg) {
 #endif
 void bdk_set_error(const std::string& m) { g_err = m; }      // bd_comm.hip reports through the same bd_last_error()
 
-#define BD_TRY(expr)                                                                     \
-    do {                                                                                 \
-        int _r = (expr);                                                                 \
-        if (_r != 0) return fail(std::string(#expr) + " failed with " + std::to_string(_r)); \
-    } while (0)
-
 // nw = waves per workgroup, kw = waves sharing one 32-column panel (split-K inside the workgroup, bd_gemm.hip), ring = K
 // stages in flight per wave, S = split-K over the grid
 struct GemmCfg { int S = 1, nw = 4, ring = 2, kw = 1, half = 0; int code() const { return nw + 16 * ring + 256 * (kw - 1) + 4096 * half; } };   // half: the 256 x 128-tile kernel (bd_gemm_half.hip)
@@ -810,10 +804,6 @@ static Partial part(const bd_ctx* c, const std::string& ws, const void* bias, in
     return Partial{(const float*)c->ptr(ws), bias, S, N, Mpad};
 }
 
-static Partial done(const bd_ctx* c, const std::string& ws, int N, int Mpad) {   // finished bf16 Linear output
-    return Partial{(const float*)c->ptr(ws), nullptr, 0, N, Mpad};
-}
-
 // Many K slices in front of a consumer with FEW workgroups (the attention of a tensor-parallel rank: 2 x heads / tp workgroups, each
 // reading its q / k / v through every slab): one row-parallel pass (a workgroup per row, every slab load in flight) sums them into the
 // finished bf16 tensor first.  "tune.finalize_s": slab count from which this runs (default: 3 under tensor parallelism, off on one GPU).
@@ -851,48 +841,58 @@ static int linear(bd_ctx* c, const char* name, const void* A, int RB, WRef W, in
     return 0;
 }
 
+// What a ROW-split Linear (wo / w2, o_proj / down_proj) left for the row kernel behind it to add to the residual stream
+struct Pending {
+    Partial part{nullptr, nullptr, 0, 0, 0};   // all-reduce / single-GPU form: the finished tensor, or the slabs + their bias
+    const void* bias = nullptr;                // sequence-parallel form: the bias the rows' owner adds, and the hand-off of this
+    int seq_p = 0;                             //   rank's partial rows in the `tp_ws` workspace (0: nothing pending)
+};
+
+// the next hand-off's sequence number; `qwen3`: drawn for a row kernel of the Qwen3 step (the text names what restarts the count)
+static int sp_next_seq(bd_ctx* c, int* seq, bool qwen3 = false) {
+    *seq = bdk_sp_next_seq(c->comm);
+    if (*seq >= 0) return 0;
+    return fail(qwen3 ? "sequence-parallel exchange: more than 65535 hand-offs in one Qwen3 step"
+                      : "sequence-parallel exchange: more than 65535 hand-offs since the last bd_head_cond / bd_head_sample");
+}
+
 // A ROW-split Linear under tensor parallelism (wo / w2 / o_proj / down_proj): this rank multiplies its K-slice into ONE
 // finished fp32 partial (grid slices, if any, reduced inside the launch), then the exchange kernel sums the ranks' partials,
 // adds the bias and rounds once (bd_comm.hip).  With one rank it is the plain Linear above.
+// `sp`, the sequence-parallel form: the GEMM's epilogue pushes every owner its rows of the fp32 partial (8-row groups round-robin,
+// BdTpPush::il); nothing else is launched -- the owner's row kernel (ln_mod_sp / head_final_sp / rms_sp) reduces, told by
+// res->seq_p which hand-off to wait for and by res->bias what to add.
 static int linear_rowsplit(bd_ctx* c, const char* name, const void* A, int RB, WRef W, int N, int Klocal, const GemmCfg& g,
                            const char* scratch_ws, const char* out_ws, const char* tp_ws, const void* bias, int Mpad, int rows,
-                           Partial* res, hipStream_t st) {
-    if (c->tp <= 1) return linear(c, name, A, RB, W, N, Klocal, g, scratch_ws, out_ws, bias, Mpad, res, st);
+                           bool sp, Pending* res, hipStream_t st) {
+    *res = Pending{};
+    if (c->tp <= 1) return linear(c, name, A, RB, W, N, Klocal, g, scratch_ws, out_ws, bias, Mpad, &res->part, st);
     if (!c->comm) return fail(std::string(name) + ": tensor-parallel context without a communicator (bd_ctx_set_comm)");
     if (g.S > 3) return fail(std::string(name) + ": a tensor-parallel partial needs at most 3 grid slices");
-    // phase 1 of the exchange (every peer's slice of the partial into that peer's staging row) fused into the GEMM's epilogue where
-    // the shape allows it: the exchange kernel then only signals, waits, reduces and pushes the result ("tune.tp_fuse" = 0: unfused)
     BdTpPush push;
     GemmCall k = gemm_call(c, A, RB, W, N, Klocal, g.S, g.code(), BD_EPI_F32, (float*)c->wptr(scratch_ws), c->wptr(tp_ws), nullptr);
     k.push = &push;
+    if (sp) {
+        if (int r = sp_next_seq(c, &res->seq_p)) return r;
+        res->bias = bias;
+        // "tune.sp_gsig" = 1: the GEMM's last workgroup signals the owners; 0 (default): the owner's row kernel's first block does -- the
+        // arrival counter + barrier at the end of every GEMM workgroup cost more than the flag's head start returns (loop-back, per
+        // evaluation: tp 8 728.6 vs 702.1 us, tp 4 761.0 vs 743.4, tp 2 918.4 vs 909.5; profiles/r05_tp_rank_critical_path.log)
+        if (!bdk_tp_push_target_sp(c->comm, rows, N, c->geti("tune.sp_gsig", 0) ? res->seq_p : 0, &push))
+            return fail(std::string(name) + ": no sequence-parallel push target for this shape");
+        if (push.done_cnt) push.done_cnt = (int*)c->wptr("gemm.cnt") + 16383;   // arrival counter in ordinary (L2-served) memory: the last counter word, never a tile's
+        if (!bdk_gemm_takes_push(k)) return fail(std::string(name) + ": the GEMM did not take the push target");
+        BD_TRY(gemm(c, name, k, st));
+        bdk_comm_count_exchange(c->comm);
+        return 0;
+    }
+    // phase 1 of the exchange (every peer's slice of the partial into that peer's staging row) fused into the GEMM's epilogue where
+    // the shape allows it: the exchange kernel then only signals, waits, reduces and pushes the result ("tune.tp_fuse" = 0: unfused)
     const bool fused = c->geti("tune.tp_fuse", 1) != 0 && bdk_tp_push_target(c->comm, rows, N, &push) && bdk_gemm_takes_push(k);
     if (!fused) k.push = nullptr;
     BD_TRY(gemm(c, name, k, st));
     if (fused) bdk_tp_mark_prepushed(c->comm);
-    BD_TRY(bdk_tp_allreduce(c->comm, (const float*)c->ptr(tp_ws), bias, rows, N, res, st));
-    return 0;
-}
-
-// Sequence-parallel form of a ROW-split Linear (wo / w2): the GEMM's epilogue pushes every owner its rows of the fp32 partial (8-row
-// groups round-robin, BdTpPush::il); nothing else is launched -- the owner's row kernel (ln_mod_sp / head_final_sp) reduces.
-// Returns the sequence number of the hand-off in *seq.
-static int linear_rowsplit_sp(bd_ctx* c, const char* name, const void* A, int RB, WRef W, int N, int Klocal, const GemmCfg& g,
-                              const char* scratch_ws, const char* tp_ws, int rows, int* seq, hipStream_t st) {
-    if (g.S > 3) return fail(std::string(name) + ": a tensor-parallel partial needs at most 3 grid slices");
-    *seq = bdk_sp_next_seq(c->comm);
-    if (*seq < 0) return fail("sequence-parallel exchange: more than 65535 hand-offs since the last bd_head_cond / bd_head_sample");
-    BdTpPush push;
-    // "tune.sp_gsig" = 1: the GEMM's last workgroup signals the owners; 0 (default): the owner's row kernel's first block does -- the
-    // arrival counter + barrier at the end of every GEMM workgroup cost more than the flag's head start returns (loop-back, per
-    // evaluation: tp 8 728.6 vs 702.1 us, tp 4 761.0 vs 743.4, tp 2 918.4 vs 909.5; profiles/r05_tp_rank_critical_path.log)
-    if (!bdk_tp_push_target_sp(c->comm, rows, N, c->geti("tune.sp_gsig", 0) ? *seq : 0, &push))
-        return fail(std::string(name) + ": no sequence-parallel push target for this shape");
-    if (push.done_cnt) push.done_cnt = (int*)c->wptr("gemm.cnt") + 16383;   // arrival counter in ordinary (L2-served) memory: the last counter word, never a tile's
-    GemmCall k = gemm_call(c, A, RB, W, N, Klocal, g.S, g.code(), BD_EPI_F32, (float*)c->wptr(scratch_ws), c->wptr(tp_ws), nullptr);
-    k.push = &push;
-    if (!bdk_gemm_takes_push(k)) return fail(std::string(name) + ": the GEMM did not take the push target");
-    BD_TRY(gemm(c, name, k, st));
-    bdk_comm_count_exchange(c->comm);
+    BD_TRY(bdk_tp_allreduce(c->comm, (const float*)c->ptr(tp_ws), bias, rows, N, &res->part, st));
     return 0;
 }
 // the wait of the consumer GEMM for the operand rows pushed with sequence number `seq`: *w for its prologue, handed to the linear() /
@@ -977,8 +977,87 @@ static int head_ada_group(bd_ctx* c, int g, hipStream_t st) {
     return 0;
 }
 
+// The activation operand a norm row kernel left for the GEMM behind it: the local workspace with its fp8 scales' name for wref(), or
+// in the sequence-parallel form the landing buffer every owner pushes its rows into, with the wait for them (sp_wait)
+struct Operand { const void* A = nullptr; const char* ascale_ws = nullptr; BdHWait wait; };
+
+// column offsets of (gate, scale, shift) in the stacked adaLN projection: half 0 / 1 of block b = what ln1 / ln2 apply (ln1's gate
+// is the one of the previous block's w2 output; the MLP head's single norm takes half 0), b = head.nblocks = the final layer
+struct AdaOffsets { int gate, scale, shift; };
+static AdaOffsets ada_offsets(const bd_ctx* c, int b, int half) {
+    const int D = c->hD, sw = c->hNB / c->hNA;
+    const int nc = c->hMlp ? 3 : 6;                           // adaLN chunks per adaLN block; the block's last gate is chunk nc - 1
+    const int base = (b / sw) * nc * D, prev_gate = ((b - 1 < 0 ? 0 : b - 1) / sw) * nc * D + (nc - 1) * D;
+    if (b == c->hNB) return {prev_gate, c->hNA * nc * D, c->hNA * nc * D + D};
+    if (half == 0) return {prev_gate, base, base + D};
+    return {base + 2 * D, base + 3 * D, base + 4 * D};
+}
+
+// x += gate * pending branch ; h = LN(x) * (1 + scale) + shift, as the next GEMM's operand.  All-reduce / single-GPU form: ln_mod over
+// every row into head.h_frag.  Sequence-parallel form (L): ln_mod_sp over this rank's rows, which draws the hand-off of its operand rows
+static int head_ln_mod(bd_ctx* c, const void* ada, AdaOffsets off, const std::string& ln_key, const Pending& pend, const BdSpLink* L,
+                       Operand* op, hipStream_t st) {
+    LnModSpArgs s;
+    LnModArgs& l = s.ln;
+    l.X = c->wptr("head.X");
+    l.pend = pend.part;
+    l.ada = ada; l.ada_ld = c->hNada;
+    l.gate_off = off.gate; l.scale_off = off.scale; l.shift_off = off.shift;
+    l.ln_w = (const float*)c->ptr(ln_key + "_w"); l.ln_b = (const float*)c->ptr(ln_key + "_b");
+    l.h_frag = nullptr; l.M = c->M; l.D = c->hD; l.RB = c->RB; l.eps = 1e-6f;
+    if (!L) {
+        l.h_frag = c->wptr("head.h_frag");
+        if (c->fp8a) l.a8_scale = (float*)c->wptr("head.h_scale");
+        l.wave_rows = (int)c->geti("tune.ln_rows", c->M >= 1024 ? 1 : 0);   // the ImageNet batch: a wave per row (bd_rows.hip)
+        BD_TRY(bdk_ln_mod(l, st));
+        *op = Operand{c->ptr("head.h_frag"), "head.h_scale", BdHWait{}};
+        return 0;
+    }
+    s.L = *L; s.rows_local = c->M / c->tp;
+    s.part = pend.seq_p ? (const float*)c->ptr("head.tp_part") : nullptr; s.bias = pend.bias; s.seq_p = pend.seq_p;
+    s.signal_p = c->geti("tune.sp_gsig", 0) ? 0 : 1;
+    if (int r = sp_next_seq(c, &s.seq_h)) return r;
+    BD_TRY(bdk_ln_mod_sp(s, st));
+    *op = Operand{bdk_sp_hbuf(c->comm), nullptr, BdHWait{}};
+    return sp_wait(c, s.seq_h, &op->wait, st);
+}
+
+static int head_attention(bd_ctx* c, const std::string& pre, const Operand& h, hipStream_t st) {
+    const int Dl = c->hDl;
+    HeadAttnArgs at;
+    BD_TRY(linear(c, "head.qkv", h.A, c->RB, wref(c, pre + "wqkv", h.ascale_ws), 3 * Dl, c->hD, c->cfg("head.qkv"), "head.qkv_part", "head.qkv_bf",
+                  c->ptr(pre + "bqkv"), c->Mpad, &at.qkv, st, false, &h.wait));
+    BD_TRY(finalize_if_many(c, &at.qkv, "head.qkv_bf", c->M, st));
+    at.o_frag = c->wptr("head.attn_frag"); at.nseq = c->M / c->Pn; at.dh = (int)c->geti("head.dh", 128); at.nhead = Dl / at.dh; at.D = Dl; at.RB = c->RB; at.P = c->Pn;
+    BD_TRY(bdk_head_attn(at, st));
+    return 0;
+}
+
+// Linear -> chunk(2) -> silu(h1)*h2.  Fused epilogue (on the last-arriving K-slice when split) writes the next
+// operand: 46.9 + 22.9 us (w1 + w2) against 40.8 + 9.5 + 26.0 us for slabs + swiglu_rows on the same MI355X
+// (tune.w1_fused = 0 selects the latter).
+// (256-row passes: slabs + swiglu_rows.  The fused epilogue behind the 256-row kernel's in-launch reduction -- "tune.w1_fused" = 1 at
+// 512 rows -- measured 25 us SLOWER per launch: the last arriver of a tile writes the whole SwiGLU tile with 2-byte stores; 2390 vs 2250 us
+// per evaluation, profiles/r05_head_sweep_b4.log)
+static int head_w1(bd_ctx* c, const std::string& pre, const Operand& h, hipStream_t st) {
+    const int D = c->hD, Hl = c->hHl, RB = c->RB;
+    const GemmCfg& g1 = c->cfg("head.w1");
+    const bool fused = g1.S == 1 || c->geti("tune.w1_fused", (c->Mpad % 256 == 0 || g1.S > 2) ? 0 : 1);
+    BD_TRY(gemm(c, "head.w1", h.A, RB, wref(c, pre + "w1", h.ascale_ws), 2 * Hl, D, g1.S, g1.code(), fused ? BD_EPI_SWIGLU : BD_EPI_PARTIAL,
+                (float*)c->wptr("head.w1_part"), fused ? c->wptr("head.act_frag") : nullptr, fused ? c->ptr(pre + "b1") : nullptr, st, &h.wait));
+    if (fused) return 0;
+    SwigluArgs sw;                                             // many short K slices + a row-parallel SwiGLU pass over the slabs
+    sw.up = part(c, "head.w1_part", c->ptr(pre + "b1"), g1.S, 2 * Hl, c->Mpad);
+    sw.act_frag = c->wptr("head.act_frag"); sw.M = c->M; sw.F = Hl; sw.RB = RB; sw.interleaved = 1;
+    BD_TRY(bdk_swiglu_rows(sw, st));
+    return 0;
+}
+
 // `ada_buf` < 0: compute y and the adaLN projection here, in line (the plain path); >= 0: this evaluation's rows of a grouped
-// projection (head_ada_group) are slot `ada_buf` of head.ada_bf
+// projection (head_ada_group) are slot `ada_buf` of head.ada_bf.
+// Per block  ln_mod -> qkv -> attention -> wo -> ln_mod -> w1 -> w2, then head_final; every ln_mod / head_final adds the gated output
+// of the row-split Linear in front of it.  Sequence-parallel form (bd_sp.hip): the row kernels run on the rows' owner, wo / w2 push it
+// their partial rows, qkv / w1 wait for its operand rows: 12 GEMMs + 6 attention + 13 row kernels, no exchange kernel.
 static int head_eval(bd_ctx* c, int i, hipStream_t st, int ada_buf = -1, bool x0_ready = false, bool chain_next = false) {
     if (i < 0 || i >= (int)c->sched.size()) return fail("bd_head_eval: eval index outside the schedule");
     const int D = c->hD, Mp = c->Mpad, RB = c->RB, M = c->M;
@@ -1000,175 +1079,73 @@ static int head_eval(bd_ctx* c, int i, hipStream_t st, int ada_buf = -1, bool x0
     }
 
     const void* ada = (const bf16_t*)c->ptr("head.ada_bf") + (size_t)ada_buf * Mp * c->hNada;
-    const int sw = c->hNB / c->hNA;
-    const bool mlp = c->hMlp != 0;
-    const int nc = mlp ? 3 : 6;                               // adaLN chunks per adaLN block; the block's last gate is chunk nc - 1
-    const GemmCfg &gq = c->cfg("head.qkv"), &go = c->cfg("head.wo"), &g1 = c->cfg("head.w1"), &g2 = c->cfg("head.w2");
-    if (c->sp) {
-        // ---- sequence-parallel evaluation (bd_sp.hip): per block  ln_mod_sp -> qkv (waits for the rows) -> attention -> wo (pushes
-        // partial rows) -> ln_mod_sp -> w1 (waits) -> w2 (pushes) ; head_final_sp.  12 GEMMs + 6 attention + 13 row kernels, no exchange kernel.
-        BdSpLink L;
-        if (!bdk_sp_link(c->comm, &L)) return fail("sequence-parallel exchange: the communicator lost its peers");
-        const int rows_local = M / c->tp;
-        int seq_p = 0;                                         // pending row-split Linear's hand-off (0: none)
-        const void* pend_bias = nullptr;
-        for (int b = 0; b < c->hNB; ++b) {
-            const std::string pre = "head.blk" + std::to_string(b) + ".";
-            const int base = (b / sw) * nc * D;
-            LnModSpArgs l1;
-            l1.ln.X = c->wptr("head.X");
-            l1.ln.ada = ada; l1.ln.ada_ld = c->hNada;
-            l1.ln.gate_off = ((b - 1 < 0 ? 0 : b - 1) / sw) * nc * D + (nc - 1) * D;
-            l1.ln.scale_off = base; l1.ln.shift_off = base + D;
-            l1.ln.h_frag = nullptr; l1.ln.M = M; l1.ln.D = D; l1.ln.RB = RB; l1.ln.eps = 1e-6f;
-            l1.ln.ln_w = (const float*)c->ptr(pre + "ln1_w"); l1.ln.ln_b = (const float*)c->ptr(pre + "ln1_b");
-            l1.L = L; l1.rows_local = rows_local;
-            l1.part = seq_p ? (const float*)c->ptr("head.tp_part") : nullptr; l1.bias = pend_bias; l1.seq_p = seq_p;
-            l1.signal_p = c->geti("tune.sp_gsig", 0) ? 0 : 1;
-            l1.seq_h = bdk_sp_next_seq(c->comm);
-            if (l1.seq_h < 0) return fail("sequence-parallel exchange: more than 65535 hand-offs since the last bd_head_cond / bd_head_sample");
-            BD_TRY(bdk_ln_mod_sp(l1, st));
-            HeadAttnArgs at;
-            BdHWait hw;
-            BD_TRY(sp_wait(c, l1.seq_h, &hw, st));
-            BD_TRY(linear(c, "head.qkv", bdk_sp_hbuf(c->comm), RB, wref(c, pre + "wqkv"), 3 * Dl, D, gq, "head.qkv_part", "head.qkv_bf",
-                          c->ptr(pre + "bqkv"), Mp, &at.qkv, st, false, &hw));
-            BD_TRY(finalize_if_many(c, &at.qkv, "head.qkv_bf", M, st));
-            at.o_frag = c->wptr("head.attn_frag"); at.nseq = M / c->Pn; at.dh = (int)c->geti("head.dh", 128); at.nhead = Dl / at.dh; at.D = Dl; at.RB = RB; at.P = c->Pn;
-            BD_TRY(bdk_head_attn(at, st));
-            BD_TRY(linear_rowsplit_sp(c, "head.wo", c->ptr("head.attn_frag"), RB, wref(c, pre + "wo"), D, Dl, go, "head.br_part", "head.tp_part", M, &seq_p, st));
-            LnModSpArgs l2 = l1;
-            l2.ln.gate_off = base + 2 * D; l2.ln.scale_off = base + 3 * D; l2.ln.shift_off = base + 4 * D;
-            l2.ln.ln_w = (const float*)c->ptr(pre + "ln2_w"); l2.ln.ln_b = (const float*)c->ptr(pre + "ln2_b");
-            l2.part = (const float*)c->ptr("head.tp_part"); l2.bias = c->ptr(pre + "bo"); l2.seq_p = seq_p;
-            l2.seq_h = bdk_sp_next_seq(c->comm);
-            if (l2.seq_h < 0) return fail("sequence-parallel exchange: more than 65535 hand-offs since the last bd_head_cond / bd_head_sample");
-            BD_TRY(bdk_ln_mod_sp(l2, st));
-            BD_TRY(sp_wait(c, l2.seq_h, &hw, st));
-            if (g1.S == 1 || c->geti("tune.w1_fused", g1.S > 2 ? 0 : 1)) {
-                BD_TRY(gemm(c, "head.w1", bdk_sp_hbuf(c->comm), RB, wref(c, pre + "w1"), 2 * Hl, D, g1.S, g1.code(), BD_EPI_SWIGLU,
-                            (float*)c->wptr("head.w1_part"), c->wptr("head.act_frag"), c->ptr(pre + "b1"), st, &hw));
-            } else {                                           // many short K slices + a row-parallel SwiGLU pass over the slabs
-                BD_TRY(gemm(c, "head.w1", bdk_sp_hbuf(c->comm), RB, wref(c, pre + "w1"), 2 * Hl, D, g1.S, g1.code(), BD_EPI_PARTIAL,
-                            (float*)c->wptr("head.w1_part"), nullptr, nullptr, st, &hw));
-                SwigluArgs sw_;
-                sw_.up = part(c, "head.w1_part", c->ptr(pre + "b1"), g1.S, 2 * Hl, Mp);
-                sw_.act_frag = c->wptr("head.act_frag"); sw_.M = M; sw_.F = Hl; sw_.RB = RB; sw_.interleaved = 1;
-                BD_TRY(bdk_swiglu_rows(sw_, st));
-            }
-            BD_TRY(linear_rowsplit_sp(c, "head.w2", c->ptr("head.act_frag"), RB, wref(c, pre + "w2"), D, Hl, g2, "head.br_part", "head.tp_part", M, &seq_p, st));
-            pend_bias = c->ptr(pre + "b2");
-        }
-        HeadFinalSpArgs fs;
-        HeadFinalArgs& fa = fs.f;
-        fa.X = c->ptr("head.X");
-        fa.pend = Partial{nullptr, nullptr, 0, 0, 0};
-        fa.ada = ada; fa.ada_ld = c->hNada;
-        fa.gate_off = ((c->hNB - 1) / sw) * nc * D + (nc - 1) * D;
-        fa.scale_off = c->hNA * nc * D; fa.shift_off = c->hNA * nc * D + D;
-        fa.lin_w = c->ptr("head.lin_w"); fa.lin_b = c->ptr("head.lin_b");
-        fa.xt = (float*)c->wptr("head.xt");
-        fa.noise = (const float*)c->ptr("head.noise");
-        fa.noise_step_stride = (long long)(n_steps + 1) * c->BP * c->hC;
-        fa.eval_index = i; fa.state = state;
-        fa.pred_out = nullptr; fa.tok_cur = nullptr; fa.tok_all = nullptr;       // written by tok_finish, on every rank
-        fa.T = c->hT; fa.P = c->Pn;
-        fa.xhat_out = c->geti("rt.dump_xhat", 0) ? (float*)c->wptr("head.xhat") : nullptr;
-        fa.sc = c->sched[i];
-        fa.BP = c->BP; fa.D = D; fa.C = c->hC; fa.M = M; fa.eps_ln = 1e-6f; fa.sigmoid = (int)c->geti("head.sigmoid", 1);
-        fa.cfg_table = (const float*)c->optr("head.cfg_table");
-        fa.tok_branches = 1;
-        if (chain_next) { fa.X_next = c->wptr("head.X"); fa.in_w = c->ptr("head.in_w"); fa.in_b = c->ptr("head.in_b"); }
-        fs.L = L; fs.part = (const float*)c->ptr("head.tp_part"); fs.bias = pend_bias; fs.seq_p = seq_p; fs.bp_local = c->BP / c->tp;
-        fs.seq_f = 0; fs.signal_p = c->geti("tune.sp_gsig", 0) ? 0 : 1;
-        if (fa.sc.is_final) {
-            fs.seq_f = bdk_sp_next_seq(c->comm);
-            if (fs.seq_f < 0) return fail("sequence-parallel exchange: more than 65535 hand-offs since the last bd_head_cond / bd_head_sample");
-        }
-        BD_TRY(bdk_head_final_sp(fs, st));
-        if (fa.sc.is_final) {
-            TokFinishArgs tf;
-            tf.L = L; tf.seq_f = fs.seq_f;
-            tf.xt = (float*)c->wptr("head.xt"); tf.pred_out = (float*)c->wptr("head.pred"); tf.tok_cur = (float*)c->wptr("head.tok_cur");
-            tf.tok_all = (float*)const_cast<void*>(c->optr("head.tok_all"));
-            tf.state = state; tf.BP = c->BP; tf.C = c->hC; tf.T = c->hT; tf.P = c->Pn;
-            tf.tok_branches = (c->geti("proj.rows_all", 0) && c->has_proj) ? c->branches : 1;
-            BD_TRY(bdk_tok_finish(tf, st));
-        }
-        return 0;
-    }
-    Partial br{nullptr, nullptr, 0, 0, 0};                    // pending gated branch output (wo / w2)
+    const GemmCfg &go = c->cfg("head.wo"), &g2 = c->cfg("head.w2");
+    BdSpLink link;
+    const BdSpLink* L = c->sp ? &link : nullptr;
+    if (c->sp && !bdk_sp_link(c->comm, &link)) return fail("sequence-parallel exchange: the communicator lost its peers");
+    Pending br;                                                // pending gated branch output (wo / w2; none for block 0)
+    Operand h;
     for (int b = 0; b < c->hNB; ++b) {
         const std::string pre = "head.blk" + std::to_string(b) + ".";
-        const int base = (b / sw) * nc * D;
-        LnModArgs l1;
-        l1.X = c->wptr("head.X");
-        l1.pend = br;                                      // w2 output of the previous block (none for block 0)
-        l1.ada = ada; l1.ada_ld = c->hNada;
-        l1.gate_off = ((b - 1 < 0 ? 0 : b - 1) / sw) * nc * D + (nc - 1) * D;
-        l1.scale_off = base; l1.shift_off = base + D;
-        l1.h_frag = c->wptr("head.h_frag"); l1.M = M; l1.D = D; l1.RB = RB; l1.eps = 1e-6f;
-        if (c->fp8a) l1.a8_scale = (float*)c->wptr("head.h_scale");
-        l1.wave_rows = (int)c->geti("tune.ln_rows", M >= 1024 ? 1 : 0);   // the ImageNet batch: a wave per row (bd_rows.hip)
-        LnModArgs l2 = l1;
-        if (!mlp) {
-            l1.ln_w = (const float*)c->ptr(pre + "ln1_w"); l1.ln_b = (const float*)c->ptr(pre + "ln1_b");
-            BD_TRY(bdk_ln_mod(l1, st));
-            HeadAttnArgs at;
-            BD_TRY(linear(c, "head.qkv", c->ptr("head.h_frag"), RB, wref(c, pre + "wqkv", "head.h_scale"), 3 * Dl, D, gq, "head.qkv_part", "head.qkv_bf",
-                          c->ptr(pre + "bqkv"), Mp, &at.qkv, st));
-            BD_TRY(finalize_if_many(c, &at.qkv, "head.qkv_bf", M, st));
-            at.o_frag = c->wptr("head.attn_frag"); at.nseq = M / c->Pn; at.dh = (int)c->geti("head.dh", 128); at.nhead = Dl / at.dh; at.D = Dl; at.RB = RB; at.P = c->Pn;
-            BD_TRY(bdk_head_attn(at, st));
+        if (!c->hMlp) {
+            if (int r = head_ln_mod(c, ada, ada_offsets(c, b, 0), pre + "ln1", br, L, &h, st)) return r;
+            BD_TRY(head_attention(c, pre, h, st));
             BD_TRY(linear_rowsplit(c, "head.wo", c->ptr("head.attn_frag"), RB, wref(c, pre + "wo"), D, Dl, go, "head.br_part", "head.br_bf",
-                                   "head.tp_part", c->ptr(pre + "bo"), Mp, M, &l2.pend, st));
-            l2.gate_off = base + 2 * D; l2.scale_off = base + 3 * D; l2.shift_off = base + 4 * D;
+                                   "head.tp_part", c->ptr(pre + "bo"), Mp, M, c->sp, &br, st));
         }
         // MLP head (diff_head.py:133-137): the block IS the second half -- h = norm(x) * (1 + scale) + shift with the block's
-        // (scale, shift) = chunks 0, 1 and the previous block's gated w2 output still pending, exactly l1's offsets above
-        l2.ln_w = (const float*)c->ptr(pre + "ln2_w"); l2.ln_b = (const float*)c->ptr(pre + "ln2_b");
-        BD_TRY(bdk_ln_mod(l2, st));
-        // Linear -> chunk(2) -> silu(h1)*h2.  Fused epilogue (on the last-arriving K-slice when split) writes the next
-        // operand: 46.9 + 22.9 us (w1 + w2) against 40.8 + 9.5 + 26.0 us for slabs + swiglu_rows on the same MI355X
-        // (tune.w1_fused = 0 selects the latter).
-        // (256-row passes: slabs + swiglu_rows.  The fused epilogue behind the 256-row kernel's in-launch reduction -- "tune.w1_fused" = 1 at
-        // 512 rows -- measured 25 us SLOWER per launch: the last arriver of a tile writes the whole SwiGLU tile with 2-byte stores; 2390 vs 2250 us
-        // per evaluation, profiles/r05_head_sweep_b4.log)
-        if (g1.S == 1 || c->geti("tune.w1_fused", (c->Mpad % 256 == 0 || g1.S > 2) ? 0 : 1)) {
-            BD_TRY(gemm(c, "head.w1", c->ptr("head.h_frag"), RB, wref(c, pre + "w1", "head.h_scale"), 2 * Hl, D, g1.S, g1.code(), BD_EPI_SWIGLU,
-                        (float*)c->wptr("head.w1_part"), c->wptr("head.act_frag"), c->ptr(pre + "b1"), st));
-        } else {
-            BD_TRY(gemm(c, "head.w1", c->ptr("head.h_frag"), RB, wref(c, pre + "w1", "head.h_scale"), 2 * Hl, D, g1.S, g1.code(), BD_EPI_PARTIAL,
-                        (float*)c->wptr("head.w1_part"), nullptr, nullptr, st));
-            SwigluArgs sw_;
-            sw_.up = part(c, "head.w1_part", c->ptr(pre + "b1"), g1.S, 2 * Hl, Mp);
-            sw_.act_frag = c->wptr("head.act_frag"); sw_.M = M; sw_.F = Hl; sw_.RB = RB; sw_.interleaved = 1;
-            BD_TRY(bdk_swiglu_rows(sw_, st));
-        }
+        // (scale, shift) = chunks 0, 1 and the previous block's gated w2 output still pending, exactly ln1's offsets
+        if (int r = head_ln_mod(c, ada, ada_offsets(c, b, c->hMlp ? 0 : 1), pre + "ln2", br, L, &h, st)) return r;
+        BD_TRY(head_w1(c, pre, h, st));
         BD_TRY(linear_rowsplit(c, "head.w2", c->ptr("head.act_frag"), RB, wref(c, pre + "w2"), D, Hl, g2, "head.br_part", "head.br_bf",
-                               "head.tp_part", c->ptr(pre + "b2"), Mp, M, &br, st));
+                               "head.tp_part", c->ptr(pre + "b2"), Mp, M, c->sp, &br, st));
     }
-    HeadFinalArgs fa;
+    const AdaOffsets off = ada_offsets(c, c->hNB, 0);
+    const int tok_branches = (c->geti("proj.rows_all", 0) && c->has_proj) ? c->branches : 1;
+    HeadFinalSpArgs fs;
+    HeadFinalArgs& fa = fs.f;
     fa.X = c->ptr("head.X");
-    fa.pend = br;
     fa.ada = ada; fa.ada_ld = c->hNada;
-    fa.gate_off = ((c->hNB - 1) / sw) * nc * D + (nc - 1) * D;
-    fa.scale_off = c->hNA * nc * D; fa.shift_off = c->hNA * nc * D + D;
+    fa.gate_off = off.gate; fa.scale_off = off.scale; fa.shift_off = off.shift;
     fa.lin_w = c->ptr("head.lin_w"); fa.lin_b = c->ptr("head.lin_b");
     fa.xt = (float*)c->wptr("head.xt");
     fa.noise = (const float*)c->ptr("head.noise");
     fa.noise_step_stride = (long long)(n_steps + 1) * c->BP * c->hC;
     fa.eval_index = i; fa.state = state;
-    fa.pred_out = (float*)c->wptr("head.pred"); fa.tok_cur = (float*)c->wptr("head.tok_cur");
-    fa.tok_all = (float*)const_cast<void*>(c->optr("head.tok_all"));
     fa.T = c->hT; fa.P = c->Pn;
     fa.xhat_out = c->geti("rt.dump_xhat", 0) ? (float*)c->wptr("head.xhat") : nullptr;
     fa.sc = c->sched[i];
     fa.BP = c->BP; fa.D = D; fa.C = c->hC; fa.M = M; fa.eps_ln = 1e-6f; fa.sigmoid = (int)c->geti("head.sigmoid", 1);
     fa.cfg_table = (const float*)c->optr("head.cfg_table");
-    fa.tok_branches = (c->geti("proj.rows_all", 0) && c->has_proj) ? c->branches : 1;
     if (chain_next) { fa.X_next = c->wptr("head.X"); fa.in_w = c->ptr("head.in_w"); fa.in_b = c->ptr("head.in_b"); }
-    BD_TRY(bdk_head_final(fa, st));
+    if (!c->sp) {
+        fa.pend = br.part;
+        fa.pred_out = (float*)c->wptr("head.pred"); fa.tok_cur = (float*)c->wptr("head.tok_cur");
+        fa.tok_all = (float*)const_cast<void*>(c->optr("head.tok_all"));
+        fa.tok_branches = tok_branches;
+        BD_TRY(bdk_head_final(fa, st));
+        return 0;
+    }
+    // sequence-parallel form: w2's partial rows come through the staging area, not as fa.pend; a rank finishes its own patch positions
+    // and, on the final evaluation, pushes their latent rows to every rank -- tok_finish then writes pred / tokens on each of them
+    fa.pend = Partial{nullptr, nullptr, 0, 0, 0};
+    fa.pred_out = nullptr; fa.tok_cur = nullptr; fa.tok_all = nullptr;
+    fa.tok_branches = 1;
+    fs.L = link; fs.part = (const float*)c->ptr("head.tp_part"); fs.bias = br.bias; fs.seq_p = br.seq_p; fs.bp_local = c->BP / c->tp;
+    fs.seq_f = 0; fs.signal_p = c->geti("tune.sp_gsig", 0) ? 0 : 1;
+    if (fa.sc.is_final) {
+        if (int r = sp_next_seq(c, &fs.seq_f)) return r;
+    }
+    BD_TRY(bdk_head_final_sp(fs, st));
+    if (fa.sc.is_final) {
+        TokFinishArgs tf;
+        tf.L = link; tf.seq_f = fs.seq_f;
+        tf.xt = (float*)c->wptr("head.xt"); tf.pred_out = (float*)c->wptr("head.pred"); tf.tok_cur = (float*)c->wptr("head.tok_cur");
+        tf.tok_all = (float*)const_cast<void*>(c->optr("head.tok_all"));
+        tf.state = state; tf.BP = c->BP; tf.C = c->hC; tf.T = c->hT; tf.P = c->Pn;
+        tf.tok_branches = tok_branches;
+        BD_TRY(bdk_tok_finish(tf, st));
+    }
     return 0;
 }
 
@@ -1228,6 +1205,22 @@ static int projector(bd_ctx* c, hipStream_t st) {
     return 0;
 }
 
+// step + 1 / kv_len += P: the next patch's position ("rt.no_advance": the host sets the cache lengths itself)
+static int step_advance(bd_ctx* c, BdStepState* state, int nseq, hipStream_t st) {
+    if (c->geti("rt.no_advance", 0)) return 0;
+    StepAdvanceArgs sa{state, nseq, c->Pn};
+    BD_TRY(bdk_step_advance(sa, st));
+    return 0;
+}
+// what a step's final norm writes: the hidden state, and with a head behind it ("rt.emit_cond", default on) the next patch's
+// condition bf16(hidden + pos[step]) as the head's operand
+static void step_outputs(const bd_ctx* c, float** hidden_out, void** cond_frag, const float** pos) {
+    const bool emit = c->geti("rt.emit_cond", 1) != 0 && c->has_head;
+    *hidden_out = (float*)c->wptr("llm.hidden");
+    *cond_frag = emit ? c->wptr("head.cond_frag") : nullptr;
+    *pos = emit ? (const float*)c->ptr("pos") : nullptr;
+}
+
 // forward_model for one 16-token block of the imagenet transformer (model_parallel.py:342-350, layers_parallel.py:229-241)
 static int llm_step_in(bd_ctx* c, hipStream_t st) {
     const int D = c->lD, F = c->lF, Mp = c->Mpad, RB = c->RB, M = c->M, nh = c->lnh;
@@ -1276,104 +1269,58 @@ static int llm_step_in(bd_ctx* c, hipStream_t st) {
         BD_TRY(linear(c, "llm.down", c->ptr("llm.act_frag"), RB, wref(c, pre + "wdown"), D, F, gd, "llm.br_part", "llm.br_bf",
                       nullptr, Mp, &br, st));
     }
-    if (!c->geti("rt.no_advance", 0)) {
-        StepAdvanceArgs sa{state, nseq < BD_MAX_SEQ ? nseq : BD_MAX_SEQ, c->Pn};
-        BD_TRY(bdk_step_advance(sa, st));
-    }
+    BD_TRY(step_advance(c, state, nseq < BD_MAX_SEQ ? nseq : BD_MAX_SEQ, st));   // (every sequence shares slot 0: any count fits the state)
     InRmsArgs rf = r1;
     rf.pend = br; rf.w = (const float*)c->ptr("llm.final_norm"); rf.a_frag = nullptr;
-    rf.hidden_out = (float*)c->wptr("llm.hidden");
-    const bool emit = c->geti("rt.emit_cond", 1) != 0 && c->has_head;
-    rf.cond_frag = emit ? c->wptr("head.cond_frag") : nullptr;
-    rf.pos = emit ? (const float*)c->ptr("pos") : nullptr;
+    step_outputs(c, &rf.hidden_out, &rf.cond_frag, &rf.pos);
     BD_TRY(bdk_in_rms(rf, st));
     return 0;
 }
 
-// The decode step with sequence-parallel row kernels (bd_sp.hip rms_sp_kernel): a rank owns rows / tp rows of the fp32 residual stream; per
-// layer  rms_sp -> qkv (waits for the operand rows) -> q/k norm + RoPE + append -> attention -> o_proj (pushes partial rows to the owners)
-// -> rms_sp -> gate/up (waits) -> down_proj (pushes) ; the final norm's rows travel as fp32 and every rank finishes hidden state and the
-// next patch's condition itself (sp_final_rows_kernel).  No stand-alone exchange kernel: 2 L + 1 hand-offs of operand rows and 2 L of
-// partial rows instead of 2 L all-reduce kernels with two flag rounds each + 2 L replicated RMSNorms.  Values: the all-reduce form's,
-// bit for bit (the partials are summed in rank order and rounded once to bf16 by the owner).
-static int llm_step_sp(bd_ctx* c, hipStream_t st) {
-    const int D = c->lD, F = c->lFl, Mp = c->Mpad, RB = c->RB, M = c->M, nh = c->lnhl, nkv = c->lnkvl;
-    const int nseq = c->branches * c->B;
-    const float eps = (float)c->getf("llm.eps", 1e-6);
-    BdStepState* state = (BdStepState*)c->wptr("state");
-    const GemmCfg &gq = c->cfg("llm.qkv"), &go = c->cfg("llm.o"), &gg = c->cfg("llm.gu"), &gd = c->cfg("llm.down");
-    const size_t layer_elems = (size_t)nseq * nkv * c->lLmax * 128;
-    BdSpLink L;
-    if (!bdk_sp_link(c->comm, &L)) return fail("sequence-parallel exchange: the communicator lost its peers");
-    BD_TRY(bdk_sp_begin(c->comm, st));                      // sequence numbers restart with every replay of the step
-    const char* const too_many = "sequence-parallel exchange: more than 65535 hand-offs in one Qwen3 step";
-    int seq_p = 0;
-    RmsSpArgs a1;
-    a1.r.R = (float*)c->wptr("llm.R");
-    a1.r.pend = Partial{nullptr, nullptr, 0, 0, 0};
-    a1.r.a_frag = nullptr; a1.r.hidden_out = nullptr; a1.r.cond_frag = nullptr; a1.r.pos = nullptr; a1.r.state = state;
-    a1.r.M = M; a1.r.D = D; a1.r.RB = RB; a1.r.P = c->Pn; a1.r.eps = eps; a1.r.bf16_stream = 0;
-    a1.L = L; a1.rows_local = M / c->tp; a1.signal_p = c->geti("tune.sp_gsig", 0) ? 0 : 1;
-    for (int l = 0; l < c->lL; ++l) {
-        const std::string pre = "llm.l" + std::to_string(l) + ".";
-        a1.r.w = c->ptr(pre + "in_norm");
-        a1.part = seq_p ? (const float*)c->ptr("llm.tp_part") : nullptr; a1.seq_p = seq_p;
-        if ((a1.seq_h = bdk_sp_next_seq(c->comm)) < 0) return fail(too_many);
-        BD_TRY(bdk_rms_sp(a1, st));
-        QkvPostArgs qa;
-        BdHWait hw;
-        BD_TRY(sp_wait(c, a1.seq_h, &hw, st));
-        BD_TRY(linear(c, "llm.qkv", bdk_sp_hbuf(c->comm), RB, wref(c, pre + "wqkv"), c->lNqkv, D, gq, "llm.qkv_part", "llm.qkv_bf", nullptr, Mp, &qa.qkv, st, false, &hw));
-        qa.qn_w = c->ptr(pre + "q_norm"); qa.kn_w = c->ptr(pre + "k_norm");
-        qa.cos = (const float*)c->ptr("llm.cos"); qa.sin = (const float*)c->ptr("llm.sin");
-        qa.q_out = c->wptr("llm.q");
-        qa.k_cache = (bf16_t*)c->wptr("llm.k_cache") + l * layer_elems;
-        qa.vt_cache = (bf16_t*)c->wptr("llm.vt_cache") + l * layer_elems;
-        qa.state = state; qa.M = M; qa.P = c->Pn; qa.nh = nh; qa.nkv = nkv; qa.Lmax = c->lLmax; qa.eps = eps; qa.rope_bf16 = 0;
-        BD_TRY(bdk_qkv_post(qa, st));
-        LlmAttnArgs aa;
-        aa.q = c->ptr("llm.q"); aa.k_cache = qa.k_cache; aa.vt_cache = qa.vt_cache;
-        aa.o_part = (float*)c->wptr("llm.attn_opart"); aa.ml_part = (float*)c->wptr("llm.attn_ml");
-        aa.o_frag = c->wptr("llm.attn_frag"); aa.state = state;
-        aa.nseq = nseq; aa.P = c->Pn; aa.nh = nh; aa.nkv = nkv; aa.Lmax = c->lLmax; aa.splits = c->lsplits; aa.RB = RB; aa.causal = 0;
-        BD_TRY(bdk_llm_attn(aa, st));
-        BD_TRY(linear_rowsplit_sp(c, "llm.o", c->ptr("llm.attn_frag"), RB, wref(c, pre + "wo"), D, nh * 128, go, "llm.br_part", "llm.tp_part", M, &seq_p, st));
-        RmsSpArgs a2 = a1;
-        a2.r.w = c->ptr(pre + "post_norm");
-        a2.part = (const float*)c->ptr("llm.tp_part"); a2.seq_p = seq_p;
-        if ((a2.seq_h = bdk_sp_next_seq(c->comm)) < 0) return fail(too_many);
-        BD_TRY(bdk_rms_sp(a2, st));
-        BD_TRY(sp_wait(c, a2.seq_h, &hw, st));
-        BD_TRY(gemm(c, "llm.gu", bdk_sp_hbuf(c->comm), RB, wref(c, pre + "wgu"), 2 * F, D, gg.S, gg.code(), BD_EPI_SWIGLU,
-                    (float*)c->wptr("llm.gu_part"), c->wptr("llm.act_frag"), nullptr, st, &hw));
-        BD_TRY(linear_rowsplit_sp(c, "llm.down", c->ptr("llm.act_frag"), RB, wref(c, pre + "wdown"), D, F, gd, "llm.br_part", "llm.tp_part", M, &seq_p, st));
+// One RMSNorm of the Qwen3 step: R += pending branch ; the normalised rows as the next GEMM's operand, or (`last`) as the step's
+// outputs.  All-reduce / single-GPU form: rms over every row.  Sequence-parallel form (L; bd_sp.hip rms_sp_kernel): the rows' owner
+// normalises and pushes; the final norm's rows travel as fp32 behind the operand region of the landing buffers and every rank
+// finishes hidden state and the next patch's condition itself (sp_final_rows_kernel)
+static int llm_rms(bd_ctx* c, RmsArgs r, const std::string& w_key, const Pending& pend, const BdSpLink* L, bool last, Operand* op, hipStream_t st) {
+    r.w = c->ptr(w_key);
+    if (!L) {
+        r.pend = pend.part;
+        if (last) {
+            step_outputs(c, &r.hidden_out, &r.cond_frag, &r.pos);
+        } else {
+            r.a_frag = c->wptr("llm.a_frag");
+            if (c->fp8a) r.a8_scale = (float*)c->wptr("llm.a_scale");
+            *op = Operand{c->ptr("llm.a_frag"), "llm.a_scale", BdHWait{}};
+        }
+        BD_TRY(bdk_rms(r, st));
+        return 0;
     }
-    if (!c->geti("rt.no_advance", 0)) {
-        StepAdvanceArgs sa{state, nseq, c->Pn};
-        BD_TRY(bdk_step_advance(sa, st));
+    RmsSpArgs a;
+    a.r = r; a.L = *L; a.rows_local = c->M / c->tp; a.signal_p = c->geti("tune.sp_gsig", 0) ? 0 : 1;
+    a.part = pend.seq_p ? (const float*)c->ptr("llm.tp_part") : nullptr; a.seq_p = pend.seq_p;
+    if (int rc = sp_next_seq(c, &a.seq_h, /*qwen3=*/true)) return rc;
+    if (last) { a.final_rows = 1; a.final_off = (long long)c->Mpad * c->lD * 2; }
+    BD_TRY(bdk_rms_sp(a, st));
+    if (!last) {
+        *op = Operand{bdk_sp_hbuf(c->comm), nullptr, BdHWait{}};
+        return sp_wait(c, a.seq_h, &op->wait, st);
     }
-    RmsSpArgs af = a1;
-    af.r.w = c->ptr("llm.final_norm");
-    af.part = seq_p ? (const float*)c->ptr("llm.tp_part") : nullptr; af.seq_p = seq_p;
-    if ((af.seq_h = bdk_sp_next_seq(c->comm)) < 0) return fail(too_many);
-    af.final_rows = 1; af.final_off = (long long)Mp * D * 2;
-    BD_TRY(bdk_rms_sp(af, st));
     SpFinalRowsArgs fr;
-    if (!bdk_sp_hwait(c->comm, af.seq_h, M, &fr.w)) return fail("sequence-parallel exchange: no flag block");
-    fr.rows = (const float*)((const char*)bdk_sp_hbuf(c->comm) + af.final_off);
-    fr.hidden_out = (float*)c->wptr("llm.hidden");
-    const bool emit = c->geti("rt.emit_cond", 1) != 0 && c->has_head;
-    fr.cond_frag = emit ? c->wptr("head.cond_frag") : nullptr;
-    fr.pos = emit ? (const float*)c->ptr("pos") : nullptr;
-    fr.state = state; fr.M = M; fr.D = D; fr.RB = RB; fr.P = c->Pn;
+    if (!bdk_sp_hwait(c->comm, a.seq_h, c->M, &fr.w)) return fail("sequence-parallel exchange: no flag block");
+    fr.rows = (const float*)((const char*)bdk_sp_hbuf(c->comm) + a.final_off);
+    step_outputs(c, &fr.hidden_out, &fr.cond_frag, &fr.pos);
+    fr.state = r.state; fr.M = c->M; fr.D = c->lD; fr.RB = c->RB; fr.P = c->Pn;
     BD_TRY(bdk_sp_final_rows(fr, st));
     return 0;
 }
 
+// The Qwen3 decode step: per layer  rms -> qkv -> q/k norm + RoPE + append -> attention -> o_proj -> rms -> gate/up -> down_proj, then the
+// final norm.  With sequence-parallel row kernels ("tp.llm_seq"): a rank owns rows / tp rows of the fp32 residual stream, qkv and gate/up
+// wait for the operand rows, o_proj and down_proj push partial rows to the owners.  No stand-alone exchange kernel: 2 L + 1 hand-offs of
+// operand rows and 2 L of partial rows instead of 2 L all-reduce kernels with two flag rounds each + 2 L replicated RMSNorms.  Values: the
+// all-reduce form's, bit for bit (the partials are summed in rank order and rounded once to bf16 by the owner).
 static int llm_step(bd_ctx* c, hipStream_t st) {
     if (c->lvariant == 1) return llm_step_in(c, st);
-    // (the once-per-image prefill -- causal blocks of prompt tokens, bf16 hidden states -- keeps the all-reduce form)
-    if (c->sp_llm && !c->geti("rt.llm_causal", 0) && !c->geti("rt.llm_bf16", 0)) return llm_step_sp(c, st);
     // nh / nkv / F: this rank's q heads, kv heads and FFN features (the full counts at tp = 1)
     const int D = c->lD, F = c->lFl, Mp = c->Mpad, RB = c->RB, M = c->M, nh = c->lnhl, nkv = c->lnkvl;
     const int nseq = c->branches * c->B;
@@ -1381,24 +1328,29 @@ static int llm_step(bd_ctx* c, hipStream_t st) {
     BdStepState* state = (BdStepState*)c->wptr("state");
     const GemmCfg &gq = c->cfg("llm.qkv"), &go = c->cfg("llm.o"), &gg = c->cfg("llm.gu"), &gd = c->cfg("llm.down");
     // prefill (once per image, eager): the same step over a block of PROMPT tokens -- causal mask, bf16 hidden states
-    // (t2i_pipeline.py:199-217); the host sets the per-sequence cache lengths itself between blocks
+    // (t2i_pipeline.py:199-217); the host sets the per-sequence cache lengths itself between blocks.  It keeps the all-reduce form
     const int causal = (int)c->geti("rt.llm_causal", 0), bf16s = (int)c->geti("rt.llm_bf16", 0);
+    const bool sp = c->sp_llm && !causal && !bf16s;
     const size_t layer_elems = (size_t)nseq * nkv * c->lLmax * 128;
-    Partial br{nullptr, nullptr, 0, 0, 0};                    // pending branch output (o_proj / down_proj)
+    BdSpLink link;
+    const BdSpLink* L = sp ? &link : nullptr;
+    if (sp) {
+        if (!bdk_sp_link(c->comm, &link)) return fail("sequence-parallel exchange: the communicator lost its peers");
+        BD_TRY(bdk_sp_begin(c->comm, st));                  // sequence numbers restart with every replay of the step
+    }
+    RmsArgs rms;                                            // what every norm of the step shares (llm_rms)
+    rms.R = (float*)c->wptr("llm.R");
+    rms.pend = Partial{nullptr, nullptr, 0, 0, 0};
+    rms.w = nullptr; rms.a_frag = nullptr; rms.hidden_out = nullptr; rms.cond_frag = nullptr; rms.pos = nullptr; rms.state = state;
+    rms.M = M; rms.D = D; rms.RB = RB; rms.P = c->Pn; rms.eps = eps; rms.bf16_stream = bf16s;
+    Pending br;                                             // pending branch output (o_proj / down_proj; none for layer 0)
+    Operand a;
     for (int l = 0; l < c->lL; ++l) {
         const std::string pre = "llm.l" + std::to_string(l) + ".";
-        RmsArgs r1;
-        r1.R = (float*)c->wptr("llm.R");
-        r1.pend = br;                                      // down_proj output of the previous layer (none for layer 0)
-        r1.w = c->ptr(pre + "in_norm"); r1.a_frag = c->wptr("llm.a_frag");
-        r1.hidden_out = nullptr; r1.cond_frag = nullptr; r1.pos = nullptr; r1.state = state;
-        r1.M = M; r1.D = D; r1.RB = RB; r1.P = c->Pn; r1.eps = eps; r1.bf16_stream = bf16s;
-        if (c->fp8a) r1.a8_scale = (float*)c->wptr("llm.a_scale");
-        BD_TRY(bdk_rms(r1, st));
-
+        if (int r = llm_rms(c, rms, pre + "in_norm", br, L, false, &a, st)) return r;
         QkvPostArgs qa;
-        BD_TRY(linear(c, "llm.qkv", c->ptr("llm.a_frag"), RB, wref(c, pre + "wqkv", "llm.a_scale"), c->lNqkv, D, gq, "llm.qkv_part", "llm.qkv_bf",
-                      nullptr, Mp, &qa.qkv, st));
+        BD_TRY(linear(c, "llm.qkv", a.A, RB, wref(c, pre + "wqkv", a.ascale_ws), c->lNqkv, D, gq, "llm.qkv_part", "llm.qkv_bf",
+                      nullptr, Mp, &qa.qkv, st, false, &a.wait));
         qa.qn_w = c->ptr(pre + "q_norm"); qa.kn_w = c->ptr(pre + "k_norm");
         qa.cos = (const float*)c->ptr("llm.cos"); qa.sin = (const float*)c->ptr("llm.sin");
         qa.q_out = c->wptr("llm.q");
@@ -1412,38 +1364,16 @@ static int llm_step(bd_ctx* c, hipStream_t st) {
         aa.o_frag = c->wptr("llm.attn_frag"); aa.state = state;
         aa.nseq = nseq; aa.P = c->Pn; aa.nh = nh; aa.nkv = nkv; aa.Lmax = c->lLmax; aa.splits = c->lsplits; aa.RB = RB; aa.causal = causal;
         BD_TRY(bdk_llm_attn(aa, st));
-
-        RmsArgs r2 = r1;
         BD_TRY(linear_rowsplit(c, "llm.o", c->ptr("llm.attn_frag"), RB, wref(c, pre + "wo"), D, nh * 128, go, "llm.br_part", "llm.br_bf",
-                               "llm.tp_part", nullptr, Mp, M, &r2.pend, st));
-        r2.w = c->ptr(pre + "post_norm");
-        BD_TRY(bdk_rms(r2, st));
-        BD_TRY(gemm(c, "llm.gu", c->ptr("llm.a_frag"), RB, wref(c, pre + "wgu", "llm.a_scale"), 2 * F, D, gg.S, gg.code(), BD_EPI_SWIGLU,
-                        (float*)c->wptr("llm.gu_part"), c->wptr("llm.act_frag"), nullptr, st));
+                               "llm.tp_part", nullptr, Mp, M, sp, &br, st));
+        if (int r = llm_rms(c, rms, pre + "post_norm", br, L, false, &a, st)) return r;
+        BD_TRY(gemm(c, "llm.gu", a.A, RB, wref(c, pre + "wgu", a.ascale_ws), 2 * F, D, gg.S, gg.code(), BD_EPI_SWIGLU,
+                    (float*)c->wptr("llm.gu_part"), c->wptr("llm.act_frag"), nullptr, st, &a.wait));
         BD_TRY(linear_rowsplit(c, "llm.down", c->ptr("llm.act_frag"), RB, wref(c, pre + "wdown"), D, F, gd, "llm.br_part", "llm.br_bf",
-                               "llm.tp_part", nullptr, Mp, M, &br, st));
+                               "llm.tp_part", nullptr, Mp, M, sp, &br, st));
     }
-    if (!c->geti("rt.no_advance", 0)) {
-        StepAdvanceArgs sa{state, nseq, c->Pn};
-        BD_TRY(bdk_step_advance(sa, st));                   // step+1 / kv_len += P: the next patch's position
-    }
-    RmsArgs rf;
-    rf.R = (float*)c->wptr("llm.R");
-    rf.pend = br;
-    rf.w = c->ptr("llm.final_norm"); rf.a_frag = nullptr;
-    rf.hidden_out = (float*)c->wptr("llm.hidden");
-    const bool emit = c->geti("rt.emit_cond", 1) != 0 && c->has_head;
-    rf.cond_frag = emit ? c->wptr("head.cond_frag") : nullptr;
-    rf.pos = emit ? (const float*)c->ptr("pos") : nullptr;
-    rf.state = state; rf.M = M; rf.D = D; rf.RB = RB; rf.P = c->Pn; rf.eps = eps; rf.bf16_stream = bf16s;
-    BD_TRY(bdk_rms(rf, st));
-    return 0;
-}
-
-struct ResetArgs { BdStepState* state; int kv[BD_MAX_SEQ]; int nseq; int step = 0; };
-__global__ void step_reset_kernel(ResetArgs a) {
-    if (threadIdx.x == 0) a.state->step = a.step;
-    if ((int)threadIdx.x < BD_MAX_SEQ) a.state->kv_len[threadIdx.x] = ((int)threadIdx.x < a.nseq) ? a.kv[threadIdx.x] : 0;
+    BD_TRY(step_advance(c, state, nseq, st));
+    return llm_rms(c, rms, "llm.final_norm", br, L, true, nullptr, st);
 }
 
 extern "C" {
@@ -1469,268 +1399,7 @@ int bd_step_reset(bd_ctx* c, const int* kv_len, int nseq, void* s) {
             for (int i = 0; i < nseq; ++i)
                 if (kv_len[i] < 0 || kv_len[i] + c->Pn > c->lLmax)
                     return fail("bd_step_reset: kv_len[" + std::to_string(i) + "] = " + std::to_string(kv_len[i]) + " outside [0, llm.Lmax - P]");
-        ResetArgs a; a.state = (BdStepState*)c->wptr("state"); a.nseq = nseq;
-        for (int i = 0; i < BD_MAX_SEQ; ++i) a.kv[i] = i < nseq ? kv_len[i] : 0;
-        BD_LAUNCH(step_reset_kernel, dim3(1), dim3(64), 0, (hipStream_t)s, a);
-        return bd_launch_status() == 0 ? 0 : fail("step_reset launch failed");)
-}
-
-// ---- the decode attentions standalone (tests): host validation, the cache lengths into `state`, then exactly the engine's launch
-static int attn_unsupported(const std::string& m) { g_err = m; return BD_ERR_UNSUPPORTED; }
-static int attn_check_lengths(const int* kv_len, int nseq, int P, int Lmax, const char* who) {
-    for (int i = 0; i < nseq; ++i)
-        if (kv_len[i] < 0 || kv_len[i] + P > Lmax)
-            return attn_unsupported(std::string(who) + ": kv_len[" + std::to_string(i) + "] = " + std::to_string(kv_len[i]) + " outside [0, Lmax - P]");
-    return 0;
-}
-static int attn_write_lengths(void* state, const int* kv_len, int nseq, hipStream_t st, int step = 0) {
-    ResetArgs a; a.state = (BdStepState*)state; a.nseq = nseq; a.step = step;
-    for (int i = 0; i < BD_MAX_SEQ; ++i) a.kv[i] = i < nseq ? kv_len[i] : 0;
-    BD_LAUNCH(step_reset_kernel, dim3(1), dim3(64), 0, st, a);
-    return bd_launch_status();
-}
-
-int bd_llm_attn(const void* q, const void* k_cache, const void* vt_cache, const int* kv_len, int nseq, int P, int nh, int nkv, int Lmax,
-                int splits, int causal, void* state, float* o_part, float* ml_part, void* o_frag, int row_blocks, void* stream) {
-    if (nseq < 1 || nseq > BD_MAX_SEQ) return attn_unsupported("bd_llm_attn: 1 <= nseq <= 64");
-    if (P < 1 || P > 64) return attn_unsupported("bd_llm_attn: 1 <= P <= 64");
-    if (nkv < 1 || nh < nkv || nh % nkv) return attn_unsupported("bd_llm_attn: nh a multiple of nkv");
-    if ((nh / nkv) * ((P + 31) / 32) * 64 > 640) return attn_unsupported("bd_llm_attn: G * ceil(P / 32) * 64 > 640 threads");
-    if (Lmax < 64 || Lmax % 64) return attn_unsupported("bd_llm_attn: Lmax a positive multiple of 64");
-    if (splits < 1) return attn_unsupported("bd_llm_attn: splits >= 1");
-    if ((long long)row_blocks * 32 < (long long)nseq * P) return attn_unsupported("bd_llm_attn: row_blocks * 32 < nseq * P");
-    if (int r = attn_check_lengths(kv_len, nseq, P, Lmax, "bd_llm_attn")) return r;
-    hipStream_t st = (hipStream_t)stream;
-    BD_TRY(attn_write_lengths(state, kv_len, nseq, st));
-    LlmAttnArgs aa;
-    aa.q = q; aa.k_cache = k_cache; aa.vt_cache = vt_cache; aa.o_part = o_part; aa.ml_part = ml_part; aa.o_frag = o_frag;
-    aa.state = (const BdStepState*)state;
-    aa.nseq = nseq; aa.P = P; aa.nh = nh; aa.nkv = nkv; aa.Lmax = Lmax; aa.splits = splits; aa.RB = row_blocks; aa.causal = causal != 0;
-    BD_TRY(bdk_llm_attn(aa, st));
-    return 0;
-}
-
-int bd_in_attn(const void* q, const void* k_cache, const void* v_cache, int kv_len, int nseq, int P, int nh, int Lmax, int causal,
-               void* state, void* o_frag, int row_blocks, void* stream) {
-    if (nseq < 1 || nh < 1) return attn_unsupported("bd_in_attn: nseq, nh >= 1");
-    if (Lmax < 64 || Lmax % 64) return attn_unsupported("bd_in_attn: Lmax a positive multiple of 64");
-    if ((long long)row_blocks * 32 < (long long)nseq * P) return attn_unsupported("bd_in_attn: row_blocks * 32 < nseq * P");
-    if (int r = attn_check_lengths(&kv_len, 1, P, Lmax, "bd_in_attn")) return r;
-    const int form = bdk_in_attn_form(P, Lmax);
-    if (form == -2) return attn_unsupported("bd_in_attn: 1 <= P <= 16");
-    if (form < 0) return attn_unsupported("bd_in_attn: Lmax too long for the score rows of the form P takes (LDS)");
-    hipStream_t st = (hipStream_t)stream;
-    BD_TRY(attn_write_lengths(state, &kv_len, 1, st));
-    InAttnArgs aa{q, (const bf16_t*)k_cache, (const bf16_t*)v_cache, o_frag, (const BdStepState*)state, nseq, P, nh, Lmax, row_blocks};
-    aa.causal = causal != 0;
-    BD_TRY(bdk_in_attn(aa, st));
-    return 0;
-}
-
-// ---- the row kernels and the DiT head attention standalone (tests): host validation, the step state into `state` where the kernel
-// reads one, then the launcher the engine calls -- which picks the kernel form -- on the caller's buffers
-static const int kMaxRowD = 1024 * 8;   // one thread per 8 channels, at most 1024 threads (row_threads, bd_rowhelp.h)
-static int rows_fill_partial(Partial* q, const void* p, const void* bias, int S, int rows, int N, int M, const char* who, bool required) {
-    q->p = nullptr; q->bias = nullptr; q->S = 0; q->N = N; q->Mpad = rows;
-    if (S < 0) {
-        if (required) return attn_unsupported(std::string(who) + ": the Linear output is required (S >= 0)");
-        return 0;
-    }
-    if (!p) return attn_unsupported(std::string(who) + ": S >= 0 without a Linear output");
-    if (rows < M) return attn_unsupported(std::string(who) + ": the Linear output has fewer rows than M");
-    if (S == 0 && bias) return attn_unsupported(std::string(who) + ": a finished bf16 tensor (S = 0) already holds its bias");
-    q->p = (const float*)p; q->bias = bias; q->S = S;
-    return 0;
-}
-static int rows_check_width(int M, int D, int row_blocks, int max_d, const char* who) {
-    if (M < 1) return attn_unsupported(std::string(who) + ": M >= 1");
-    if (D < 8 || D % 8 || D > max_d) return attn_unsupported(std::string(who) + ": D a multiple of 8, at most " + std::to_string(max_d));
-    if ((long long)row_blocks * 32 < (long long)M) return attn_unsupported(std::string(who) + ": row_blocks * 32 < M");
-    return 0;
-}
-static int rows_check_ada(int ada_ld, int D, const int* offs, int n, const char* who) {
-    if (ada_ld < D || ada_ld % 8) return attn_unsupported(std::string(who) + ": ada_ld a multiple of 8, at least D");
-    for (int i = 0; i < n; ++i)
-        if (offs[i] < 0 || offs[i] % 8 || offs[i] + D > ada_ld)
-            return attn_unsupported(std::string(who) + ": gate / scale / shift offsets multiples of 8 inside [0, ada_ld - D]");
-    return 0;
-}
-static int rows_check_pos(const void* cond_frag, const float* pos, int pos_rows, int step, int P, const char* who) {
-    if (step < 0) return attn_unsupported(std::string(who) + ": step >= 0");
-    if (P < 1) return attn_unsupported(std::string(who) + ": P >= 1");
-    if (cond_frag && (!pos || (long long)(step + 1) * P > pos_rows))
-        return attn_unsupported(std::string(who) + ": cond_frag needs a position table of at least (step + 1) * P rows");
-    return 0;
-}
-
-int bd_ln_mod(void* X, const void* pend, const void* pend_bias, int pend_S, int pend_rows, const void* ada, int ada_ld, int gate_off,
-              int scale_off, int shift_off, const float* ln_w, const float* ln_b, void* h_frag, float* a8_scale, int M, int D,
-              int row_blocks, float eps, int wave_rows, void* stream) {
-    if (int r = rows_check_width(M, D, row_blocks, kMaxRowD, "bd_ln_mod")) return r;
-    if (!X || !ada || !h_frag) return attn_unsupported("bd_ln_mod: X, ada and h_frag are required");
-    const int offs[3] = {gate_off, scale_off, shift_off};
-    if (int r = rows_check_ada(ada_ld, D, offs, 3, "bd_ln_mod")) return r;
-    if ((ln_w == nullptr) != (ln_b == nullptr)) return attn_unsupported("bd_ln_mod: LayerNorm weight and bias come together");
-    if (a8_scale && D % 64) return attn_unsupported("bd_ln_mod: the fp8 operand needs D a multiple of 64");
-    if (wave_rows && (a8_scale || D > 1024)) return attn_unsupported("bd_ln_mod: wave_rows is the bf16 form for D <= 1024");
-    LnModArgs a{};
-    if (int r = rows_fill_partial(&a.pend, pend, pend_bias, pend_S, pend_rows, D, M, "bd_ln_mod", false)) return r;
-    a.X = X; a.ada = ada; a.ada_ld = ada_ld; a.gate_off = gate_off; a.scale_off = scale_off; a.shift_off = shift_off;
-    a.ln_w = ln_w; a.ln_b = ln_b; a.h_frag = h_frag; a.M = M; a.D = D; a.RB = row_blocks; a.eps = eps; a.a8_scale = a8_scale;
-    a.wave_rows = wave_rows != 0;
-    BD_TRY(bdk_ln_mod(a, (hipStream_t)stream));
-    return 0;
-}
-
-int bd_rms(float* R, const void* pend, const void* pend_bias, int pend_S, int pend_rows, const void* w, void* a_frag, float* a8_scale,
-           float* hidden_out, void* cond_frag, const float* pos, int pos_rows, int step, void* state, int M, int D, int P, int row_blocks,
-           float eps, int bf16_stream, void* stream) {
-    if (int r = rows_check_width(M, D, row_blocks, kMaxRowD, "bd_rms")) return r;
-    if (!R || !w || !state) return attn_unsupported("bd_rms: R, w and state are required");
-    if (a8_scale && (!a_frag || D % 64)) return attn_unsupported("bd_rms: the fp8 operand needs a_frag and D a multiple of 64");
-    if (int r = rows_check_pos(cond_frag, pos, pos_rows, step, P, "bd_rms")) return r;
-    RmsArgs a{};
-    if (int r = rows_fill_partial(&a.pend, pend, pend_bias, pend_S, pend_rows, D, M, "bd_rms", false)) return r;
-    hipStream_t st = (hipStream_t)stream;
-    BD_TRY(attn_write_lengths(state, nullptr, 0, st, step));
-    a.R = R; a.w = w; a.a_frag = a_frag; a.hidden_out = hidden_out; a.cond_frag = cond_frag; a.pos = pos;
-    a.state = (const BdStepState*)state; a.M = M; a.D = D; a.RB = row_blocks; a.P = P; a.eps = eps; a.a8_scale = a8_scale;
-    a.bf16_stream = bf16_stream != 0;
-    BD_TRY(bdk_rms(a, st));
-    return 0;
-}
-
-int bd_qkv_post(const void* qkv, const void* qkv_bias, int qkv_S, int qkv_rows, const void* qn_w, const void* kn_w, const float* cos,
-                const float* sin, int maxpos, void* q_out, void* k_cache, void* vt_cache, const int* kv_len, int nseq, int P, int nh,
-                int nkv, int Lmax, float eps, int rope_bf16, void* state, void* stream) {
-    if (nseq < 1 || nseq > BD_MAX_SEQ) return attn_unsupported("bd_qkv_post: 1 <= nseq <= 64");
-    if (P < 1 || nh < 1 || nkv < 1 || Lmax < 1) return attn_unsupported("bd_qkv_post: P, nh, nkv, Lmax >= 1");
-    if (!qn_w || !kn_w || !cos || !sin || !q_out || !k_cache || !vt_cache || !state || !kv_len)
-        return attn_unsupported("bd_qkv_post: null pointer");
-    if (int r = attn_check_lengths(kv_len, nseq, P, Lmax, "bd_qkv_post")) return r;
-    for (int i = 0; i < nseq; ++i)
-        if (kv_len[i] + P > maxpos) return attn_unsupported("bd_qkv_post: kv_len + P past the RoPE table");
-    QkvPostArgs a{};
-    if (int r = rows_fill_partial(&a.qkv, qkv, qkv_bias, qkv_S, qkv_rows, (nh + 2 * nkv) * 128, nseq * P, "bd_qkv_post", true)) return r;
-    hipStream_t st = (hipStream_t)stream;
-    BD_TRY(attn_write_lengths(state, kv_len, nseq, st));
-    a.qn_w = qn_w; a.kn_w = kn_w; a.cos = cos; a.sin = sin; a.q_out = q_out; a.k_cache = k_cache; a.vt_cache = vt_cache;
-    a.state = (const BdStepState*)state; a.M = nseq * P; a.P = P; a.nh = nh; a.nkv = nkv; a.Lmax = Lmax; a.eps = eps;
-    a.rope_bf16 = rope_bf16 != 0;
-    BD_TRY(bdk_qkv_post(a, st));
-    return 0;
-}
-
-int bd_head_attn(const void* qkv, const void* qkv_bias, int qkv_S, int qkv_rows, void* o_frag, int nseq, int nhead, int P, int dh,
-                 int row_blocks, void* stream) {
-    if (nseq < 1 || nhead < 1) return attn_unsupported("bd_head_attn: nseq, nhead >= 1");
-    if (!(P == 64 || (P >= 1 && P <= 16))) return attn_unsupported("bd_head_attn: P = 64 or 1 <= P <= 16");
-    if (dh != 128 && !(dh == 64 && P <= 16)) return attn_unsupported("bd_head_attn: head_dim 128, or 64 with P <= 16");
-    if (!o_frag) return attn_unsupported("bd_head_attn: o_frag is required");
-    if ((long long)row_blocks * 32 < (long long)nseq * P) return attn_unsupported("bd_head_attn: row_blocks * 32 < nseq * P");
-    HeadAttnArgs a{};
-    if (int r = rows_fill_partial(&a.qkv, qkv, qkv_bias, qkv_S, qkv_rows, 3 * nhead * dh, nseq * P, "bd_head_attn", true)) return r;
-    a.o_frag = o_frag; a.nseq = nseq; a.nhead = nhead; a.D = nhead * dh; a.RB = row_blocks; a.P = P; a.dh = dh;
-    BD_TRY(bdk_head_attn(a, (hipStream_t)stream));
-    return 0;
-}
-
-int bd_head_final(const void* X, const void* pend, const void* pend_bias, int pend_S, int pend_rows, const void* ada, int ada_ld,
-                  int gate_off, int scale_off, int shift_off, const void* lin_w, const void* lin_b, float* xt, const float* noise,
-                  int noise_evals, int noise_steps, int eval_index, int step, void* state, float* pred_out, float* tok_cur, float* tok_all,
-                  int T, int P, float* xhat_out, const float* scalars7, int is_final, int cfg_mult, int BP, int D, int C, float eps_ln,
-                  int sigmoid, const float* cfg_table, int cfg_table_len, int tok_branches, void* X_next, const void* in_w, const void* in_b,
-                  void* stream) {
-    if (cfg_mult != 1 && cfg_mult != 2) return attn_unsupported("bd_head_final: cfg_mult 1 or 2");
-    if (BP < 1) return attn_unsupported("bd_head_final: BP >= 1");
-    if (D < 8 || D % 8 || D > 640 * 8) return attn_unsupported("bd_head_final: D a multiple of 8, at most 5120");
-    if (C < 1 || C > 32) return attn_unsupported("bd_head_final: 1 <= C <= 32");
-    if (!X || !ada || !lin_w || !lin_b || !xt || !state || !scalars7) return attn_unsupported("bd_head_final: null pointer");
-    const int offs[3] = {gate_off, scale_off, shift_off};
-    if (int r = rows_check_ada(ada_ld, D, offs, 3, "bd_head_final")) return r;
-    if (step < 0 || P < 1) return attn_unsupported("bd_head_final: step >= 0, P >= 1");
-    if (is_final) {
-        if (tok_branches < 1) return attn_unsupported("bd_head_final: tok_branches >= 1");
-        if (tok_all && (BP % P || (long long)(step + 1) * P > T)) return attn_unsupported("bd_head_final: tok_all needs BP a multiple of P and (step + 1) * P <= T");
-    } else {
-        if (!noise || step >= noise_steps || eval_index < 0 || eval_index + 1 >= noise_evals)
-            return attn_unsupported("bd_head_final: a non-final step reads noise[step][eval_index + 1] inside [noise_steps][noise_evals]");
-        if (X_next && (!in_w || !in_b)) return attn_unsupported("bd_head_final: X_next needs the input projection");
-    }
-    if (cfg_table && step >= cfg_table_len) return attn_unsupported("bd_head_final: step past the guidance table");
-    HeadFinalArgs a{};
-    if (int r = rows_fill_partial(&a.pend, pend, pend_bias, pend_S, pend_rows, D, cfg_mult * BP, "bd_head_final", false)) return r;
-    hipStream_t st = (hipStream_t)stream;
-    BD_TRY(attn_write_lengths(state, nullptr, 0, st, step));
-    a.X = X; a.ada = ada; a.ada_ld = ada_ld; a.gate_off = gate_off; a.scale_off = scale_off; a.shift_off = shift_off;
-    a.lin_w = lin_w; a.lin_b = lin_b; a.xt = xt; a.noise = noise; a.noise_step_stride = (long long)noise_evals * BP * C;
-    a.eval_index = eval_index; a.state = (const BdStepState*)state; a.pred_out = pred_out; a.tok_cur = tok_cur; a.tok_all = tok_all;
-    a.T = T; a.P = P; a.xhat_out = xhat_out;
-    a.sc.t = scalars7[0]; a.sc.dt = scalars7[1]; a.sc.den = scalars7[2]; a.sc.var = scalars7[3]; a.sc.omt = scalars7[4];
-    a.sc.noise_scale = scalars7[5]; a.sc.cfg = scalars7[6]; a.sc.is_final = is_final != 0; a.sc.cfg_mult = cfg_mult;
-    a.BP = BP; a.D = D; a.C = C; a.M = cfg_mult * BP; a.eps_ln = eps_ln; a.sigmoid = sigmoid != 0; a.cfg_table = cfg_table;
-    a.tok_branches = tok_branches; a.X_next = X_next; a.in_w = in_w; a.in_b = in_b;
-    BD_TRY(bdk_head_final(a, st));
-    return 0;
-}
-
-int bd_swiglu_rows(const void* up, const void* up_bias, int up_S, int up_rows, void* act_frag, int M, int F, int row_blocks,
-                   int interleaved, void* stream) {
-    if (M < 1) return attn_unsupported("bd_swiglu_rows: M >= 1");
-    if (F < 8 || F % 8 || (interleaved && F % 16)) return attn_unsupported("bd_swiglu_rows: F a multiple of 8 (16 for the interleaved column order)");
-    if ((long long)row_blocks * 32 < (long long)M) return attn_unsupported("bd_swiglu_rows: row_blocks * 32 < M");
-    if (!act_frag) return attn_unsupported("bd_swiglu_rows: act_frag is required");
-    SwigluArgs a{};
-    if (int r = rows_fill_partial(&a.up, up, up_bias, up_S, up_rows, 2 * F, M, "bd_swiglu_rows", true)) return r;
-    a.act_frag = act_frag; a.M = M; a.F = F; a.RB = row_blocks; a.interleaved = interleaved != 0;
-    BD_TRY(bdk_swiglu_rows(a, (hipStream_t)stream));
-    return 0;
-}
-
-int bd_in_rms(float* R, const void* pend, const void* pend_bias, int pend_S, int pend_rows, int init_from_pend, int renorm_to_R,
-              const float* w, void* a_frag, float* hidden_out, void* cond_frag, const float* pos, int pos_rows, int step, void* state,
-              int M, int D, int P, int row_blocks, float eps, int f32_stream, void* stream) {
-    if (int r = rows_check_width(M, D, row_blocks, kMaxRowD, "bd_in_rms")) return r;
-    if (!R || !w || !state) return attn_unsupported("bd_in_rms: R, w and state are required");
-    if (int r = rows_check_pos(cond_frag, pos, pos_rows, step, P, "bd_in_rms")) return r;
-    InRmsArgs a{};
-    if (int r = rows_fill_partial(&a.pend, pend, pend_bias, pend_S, pend_rows, D, M, "bd_in_rms", init_from_pend != 0)) return r;
-    hipStream_t st = (hipStream_t)stream;
-    BD_TRY(attn_write_lengths(state, nullptr, 0, st, step));
-    a.R = R; a.init_from_pend = init_from_pend != 0; a.renorm_to_R = renorm_to_R != 0; a.w = w; a.a_frag = a_frag;
-    a.hidden_out = hidden_out; a.cond_frag = cond_frag; a.pos = pos; a.state = (const BdStepState*)state;
-    a.M = M; a.D = D; a.RB = row_blocks; a.P = P; a.eps = eps; a.f32_stream = f32_stream != 0;
-    BD_TRY(bdk_in_rms(a, st));
-    return 0;
-}
-
-int bd_in_qkv_post(const void* qkv, const void* qkv_bias, int qkv_S, int qkv_rows, const float* rope, int rope_rows, void* q_out,
-                   void* k_cache, void* v_cache, int kv_len, int nseq, int P, int nh, int Lmax, void* state, void* stream) {
-    if (nseq < 1 || P < 1 || nh < 1 || Lmax < 1) return attn_unsupported("bd_in_qkv_post: nseq, P, nh, Lmax >= 1");
-    if (!rope || !q_out || !k_cache || !v_cache || !state) return attn_unsupported("bd_in_qkv_post: null pointer");
-    if (int r = attn_check_lengths(&kv_len, 1, P, Lmax, "bd_in_qkv_post")) return r;
-    if (kv_len + P > rope_rows) return attn_unsupported("bd_in_qkv_post: kv_len + P past the RoPE table");
-    InQkvPostArgs a{};
-    if (int r = rows_fill_partial(&a.qkv, qkv, qkv_bias, qkv_S, qkv_rows, 3 * nh * 64, nseq * P, "bd_in_qkv_post", true)) return r;
-    hipStream_t st = (hipStream_t)stream;
-    BD_TRY(attn_write_lengths(state, &kv_len, 1, st));
-    a.rope = rope; a.q_out = q_out; a.k_cache = (bf16_t*)k_cache; a.v_cache = (bf16_t*)v_cache; a.state = (const BdStepState*)state;
-    a.M = nseq * P; a.P = P; a.nh = nh; a.Lmax = Lmax;
-    BD_TRY(bdk_in_qkv_post(a, st));
-    return 0;
-}
-
-int bd_head_y_all(const void* cemb, const void* temb, void* y_all, float* a8_scale, int M, int D, int row_blocks, int n_evals, int G,
-                  void* stream) {
-    if (int r = rows_check_width(M, D, row_blocks, kMaxRowD, "bd_head_y_all")) return r;
-    if (!cemb || !temb || !y_all) return attn_unsupported("bd_head_y_all: null pointer");
-    if (n_evals < 1 || n_evals > 65535) return attn_unsupported("bd_head_y_all: 1 <= n_evals <= 65535");
-    if (G < 1 || (G > 1 && (row_blocks * G) % 8)) return attn_unsupported("bd_head_y_all: G >= 1, and row_blocks * G a multiple of 8 when G > 1");
-    if (a8_scale && D % 64) return attn_unsupported("bd_head_y_all: the fp8 operand needs D a multiple of 64");
-    HeadYAllArgs a{cemb, temb, y_all, M, D, row_blocks, row_blocks * 32, n_evals, G};
-    a.a8_scale = a8_scale;
-    BD_TRY(bdk_head_y_all(a, (hipStream_t)stream));
-    return 0;
+        return bdk_step_reset((BdStepState*)c->wptr("state"), kv_len, nseq, 0, (hipStream_t)s) == 0 ? 0 : fail("step_reset launch failed");)
 }
 
 int bd_prof_enable(bd_ctx* c, int on) {

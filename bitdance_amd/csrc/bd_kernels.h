@@ -9,6 +9,14 @@
 #define BD_LAUNCH(...) do { (void)hipGetLastError(); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
 static inline int bd_launch_status() { return hipGetLastError() == hipSuccess ? 0 : -1; }
 
+// the C ABI's translation units (bd_api.hip, bd_api_kernels.hip): a failed launcher becomes the entry point's error text through
+// the unit's own `int fail(const std::string&)`
+#define BD_TRY(expr)                                                                     \
+    do {                                                                                 \
+        int _r = (expr);                                                                 \
+        if (_r != 0) return fail(std::string(#expr) + " failed with " + std::to_string(_r)); \
+    } while (0)
+
 // Opt a kernel in to more than 64 KiB of dynamic LDS.  The attribute is PER DEVICE: a process that drives a second GPU later
 // (replicas in one process, tests that move between devices) must set it there too, so the "done" state is a bit per device id
 // in `*done_mask` (one static word per call site / kernel instantiation), not a process-wide once-flag.
@@ -282,6 +290,8 @@ int bdk_in_attn_form(int P, int Lmax);   // 0 small, 1 matrix-pipe, 2 generic fo
 
 struct StepAdvanceArgs { BdStepState* state; int nseq, P; };
 int bdk_step_advance(const StepAdvanceArgs& a, hipStream_t st);
+// state->step = step ; kv_len[i] = the first nseq (<= BD_MAX_SEQ) entries of the HOST array kv_len, 0 behind them
+int bdk_step_reset(BdStepState* state, const int* kv_len, int nseq, int step, hipStream_t st);
 
 int bdk_gfq_indices(const float* z, int* idx, int ntok, int ncb, int bits, hipStream_t st);
 int bdk_gfq_codes(const int* idx, float* code, int ntok, int ncb, int bits, hipStream_t st);

@@ -813,6 +813,18 @@ int bdk_step_advance(const StepAdvanceArgs& a, hipStream_t st) {
     return bd_launch_status();
 }
 
+struct ResetArgs { BdStepState* state; int kv[BD_MAX_SEQ]; int nseq; int step = 0; };
+__global__ void step_reset_kernel(ResetArgs a) {
+    if (threadIdx.x == 0) a.state->step = a.step;
+    if ((int)threadIdx.x < BD_MAX_SEQ) a.state->kv_len[threadIdx.x] = ((int)threadIdx.x < a.nseq) ? a.kv[threadIdx.x] : 0;
+}
+int bdk_step_reset(BdStepState* state, const int* kv_len, int nseq, int step, hipStream_t st) {
+    ResetArgs a; a.state = state; a.nseq = nseq; a.step = step;
+    for (int i = 0; i < BD_MAX_SEQ; ++i) a.kv[i] = i < nseq ? kv_len[i] : 0;
+    BD_LAUNCH(step_reset_kernel, dim3(1), dim3(64), 0, st, a);
+    return bd_launch_status();
+}
+
 // ------------------------------------------------------------------------------------------------
 // Group-wise lookup-free quantiser index math (imagenet_gen/src/gfq.py:217-239, :152-160): integer, bit exact.
 //   quantise: idx[t][c] = sum_k (z[t][c*bits + k] > 0) << k ;   codes: code[t][c*bits + k] = bit k of idx ? +1 : -1
